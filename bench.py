@@ -33,12 +33,9 @@ import json
 import os
 import sys
 import time
+import zlib
 
-# The serving loop keeps 2 dense + up to 4 search streams (+ their side streams) busy; with ROCm's default of 4 hardware queues
-# per process several of them share one in-order queue and a search stage waits behind whole dense graphs (search latency
-# 10.5 -> 7 ms, 143 -> 158 samples/s measured with 16).  Must be set before the HIP runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -251,6 +248,59 @@ def drain_gathers():
     if GATHERER[0] is not None:
         out = GATHERER[0].drain() or out
     return out
+
+
+DUMP_BYTES = 60 << 20      # --dump-outputs: data bytes of all arrays together (the .npy headers stay well under the 64 MB cap)
+
+
+def _arrays_of(name, obj, into):
+    """{name: tensor / ndarray} of a step's result; dict keys and list positions are joined with '.'.  A ``core.Rows`` volume
+    contributes its C channels."""
+    if isinstance(obj, core.Rows):
+        obj = obj.t[:, obj.coff:obj.coff + obj.C]
+    if torch.is_tensor(obj) or isinstance(obj, np.ndarray):
+        into[name] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _arrays_of("%s.%s" % (name, k) if name else str(k), v, into)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _arrays_of("%s.%d" % (name, i), v, into)
+
+
+def host_arrays(out, cascade_ratio):
+    """What the caller of the timed path receives from one step, on the host: float64 stays float64, other floats become float32,
+    integers and bools float64 (exact).  A captured (hipGraph) dense stage hands back capacity-sized fine outputs and their count on
+    the device; they are cut to the count, as ``COOCC_Ray.simple_test`` does, so that the graph and eager paths dump the same arrays."""
+    out = dict(out) if isinstance(out, dict) else {"out": out}
+    if torch.is_tensor(out.get("fine_count")) and out.get("output_voxels_fine") is not None:
+        n = int(out["fine_count"].item()) * cascade_ratio ** 3
+        out["output_voxels_fine"] = [out["output_voxels_fine"][0][:n]]
+        out["output_coords_fine"] = [out["output_coords_fine"][0].reshape(-1)[:3 * n].view(3, n)]
+    arrs = {}
+    _arrays_of("", out, arrs)
+    res = {}
+    for k, a in arrs.items():
+        if torch.is_tensor(a):
+            a = a.detach()
+            a = (a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()).cpu().numpy()
+        res[k] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "biu" else np.float32)
+    return res
+
+
+def dump_outputs(arrays, d, limit=DUMP_BYTES):
+    """Writes ``d/<name>.npy``, ``limit`` bytes of data in all: arrays are taken smallest first, each in full when it fits its even
+    share of what is left, else as a fixed sample (seeded by its name) of that many elements, flattened, in index order."""
+    os.makedirs(d, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0]))
+    left = limit
+    for j, (name, a) in enumerate(items):
+        share = left // (len(items) - j)
+        if a.nbytes > share:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def usable_cores():
@@ -597,8 +647,11 @@ def train_main(args, model, dev, rank, world, seen_world, backend_name):
     model.train()
     g = torch.Generator(device=dev).manual_seed(1)
     N, D, fH, fW = s["gemo"].shape[1:5]
-    rgb_gt = torch.rand(N * fH * 16 * fW * 16, 3, device=dev)
-    depth_gt = torch.rand(N * fH * 16 * fW * 16, device=dev) * 50
+    # render targets from a seeded generator of their own: the same every run (the default generators are seeded per process),
+    # and g's stream of fine-voxel draws stays untouched
+    tg = torch.Generator(device=dev).manual_seed(2 + 17 * rank)
+    rgb_gt = torch.rand(N * fH * 16 * fW * 16, 3, device=dev, generator=tg)
+    depth_gt = torch.rand(N * fH * 16 * fW * 16, device=dev, generator=tg) * 50
     render = c["grid"][0] >= 100 and c["grid"][1] >= 100 and c["grid"][2] >= 8
     img = s["img"].clone().requires_grad_()
     # the index search of the NEXT step runs on a side stream under this step (the indices depend on the batch, not on the
@@ -626,6 +679,7 @@ def train_main(args, model, dev, rank, world, seen_world, backend_name):
             L = ag.render_losses(res["rgbs"].reshape(-1, 3), res["depths"].reshape(-1), rgb_gt, depth_gt, D)
             loss = loss + L["loss_rgb"] + L["loss_depth_render"]
         loss.backward()
+        return res, loss
     for _ in range(max(1, args.warmup)):
         step()
     core.TIMER.enabled, core.TIMER.only = (0 if args.no_kernel_timing else 1), ("k_wgrad", "k_gemm", "k_conv", "conv_fwd", "conv_dgrad")
@@ -634,12 +688,16 @@ def train_main(args, model, dev, rank, world, seen_world, backend_name):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     cdist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     core.check_h2_overflow()       # forward and backward operands of the last step stayed inside the f16 range
     core.TIMER.enabled = False
+    if args.dump_outputs and rank == 0:
+        res, loss = last
+        grads = {n: p.grad for n, p in model.named_parameters()}
+        dump_outputs(host_arrays(dict(res, loss=loss, img_grad=img.grad, grad=grads), model.pts_bbox_head.cascade_ratio), args.dump_outputs)
     dt = cdist.max_over_ranks(dt, dev)
     windows = [dt]                  # the training line times ONE window of --steps steps (a step is 25-30 ms)
     ksum = core.TIMER.summary()
@@ -744,9 +802,10 @@ def main():
                          "LOOP (custom_single_gpu_test, P/coocc/apis/test.py:22-60) = co_occ_amd.apis.pipelined_test with ground truth "
                          "per sample: SC / SSC confusion matrices computed on the device and delivered to the host as numpy arrays, "
                          "every sample's result dict yielded in order")
-    ap.add_argument("--windows", type=int, default=3,
-                    help="timed windows of --steps steps each (barrier + synchronize on both sides of every window); the line reports the "
-                         "MEDIAN window (value, ms_per_step) and all of them (window_ms_per_step, spread_pct)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="the --steps timed steps are split into this many consecutive windows (barrier + synchronize on both sides of "
+                         "every window; each window fills and drains the pipeline); value / ms_per_step cover all timed steps, "
+                         "window_ms_per_step / spread_pct each window")
     ap.add_argument("--slots", type=int, default=6, help="--graph 1: samples in flight (1 in its dense stage + slots-1 in the prefetched search)")
     ap.add_argument("--shard", default="samples", choices=["samples", "rays"],
                     help="samples (default): one scene per GPU, weak scaling (configs[3]).  rays: ONE scene over all ranks -- K / G / C "
@@ -754,14 +813,20 @@ def main():
                          "strong scaling: value = scenes/s of the whole job")
     ap.add_argument("--also", default="auto",
                     help="a second, SHORT measurement appended to the JSON line as \"also\": {name: {value, ms_per_step, ...}} -- north_star's literal "
-                         "stress workload (--config stress200_r101: 200x200x16 fused grid + 6 x 896 x 1600 frames), 2 windows x 10 steps in a "
+                         "stress workload (--config stress200_r101: 200x200x16 fused grid + 6 x 896 x 1600 frames), 20 steps in 2 windows in a "
                          "child process after the main measurement (<= 25 s).  auto: only for the default command's workload (config r50, "
                          "serving API, one GPU, no --train / --with-lidar / --shard rays); none: never; or a config name")
     ap.add_argument("--diag", action="store_true", help="host-side issue times per sample to stderr")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel event timing table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all; an array that does not fit is written as a fixed seeded sample of its elements, "
+                         "flattened, without its shape or indices (the same elements in every run with the same arguments)")
     args = ap.parse_args()
+    if args.steps < 1 or args.windows < 1:
+        ap.error("--steps and --windows must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU
@@ -818,7 +883,18 @@ def main():
 
     S = len(streams)
     pipe = Pipeline(model, samples, dev, streams, prefetch=bool(args.prefetch), world=world)
-    run, tpool = (lambda n, timed, S=S: pipe.run(n, S)), pipe.tpool
+    last = [None]
+
+    def keep(n, timed):
+        """``collect`` of a run of n steps: under --dump-outputs a timed run keeps the result of its last step in ``last``."""
+        if not (timed and args.dump_outputs):
+            return None
+
+        def collect(i, out):
+            if i == n - 1:
+                last[0] = out
+        return collect
+    run, tpool = (lambda n, timed, S=S: pipe.run(n, S, collect=keep(n, timed))), pipe.tpool
 
     with torch.no_grad():
         step(model, samples[0], world)          # packs weights, sizes workspaces (untimed, extra to --warmup)
@@ -852,7 +928,7 @@ def main():
 
         def run(n, timed, S=1):
             gp.time_dense = timed and os.environ.get("COOCC_BENCH_TIME_DENSE", "1") != "0"
-            gp.run(frames, n)
+            gp.run(frames, n, collect=keep(n, timed))
             with torch.cuda.stream(gp.dense_streams[0]):
                 drain_gathers()
             for ds_ in gp.dense_streams:
@@ -871,6 +947,8 @@ def main():
                     o = model.simple_test(**st_kw[i % len(st_kw)])
                     if world > 1:
                         _gather(o)
+            if timed:
+                last[0] = o
             drain_gathers()
             torch.cuda.synchronize()
         run(3, False)
@@ -906,6 +984,8 @@ def main():
                 pt_seen[0] += int(res["SSC_metric_fine" if "SSC_metric_fine" in res else "SSC_metric"].sum() > 0)
                 if world > 1:
                     _gather(res)
+            if timed:
+                last[0] = res
             drain_gathers()
             torch.cuda.synchronize()
         run(2 * max(2, args.slots), False)
@@ -927,15 +1007,17 @@ def main():
         S = 2 if tt[2] < tt[1] else 1
         probe = dict(samples_per_burst=nprobe, bursts_each=2, samples_per_s={k: round(2 * nprobe / v, 2) for k, v in tt.items()},
                      chosen=S)
-        run = (lambda n, timed, S=S: pipe.run(n, S))
+        run = (lambda n, timed, S=S: pipe.run(n, S, collect=keep(n, timed)))
     run(args.warmup, False)
     graphish = gp is not None or st_api is not None       # the dense stage is a captured graph: no per-launch events inside the timed region
     if not graphish:
         core.TIMER.enabled = 0 if args.no_kernel_timing else (2 if args.kernel_table else 1)
     core.TIMER.only = ("k_conv", "k_gemm", "k_render_nearest", "k_lift_splat")      # what the roofline objects below need
     core.TIMER.reset()
+    # the --steps timed steps, split into consecutive windows of (nearly) equal size
+    nwin = min(args.windows, args.steps)
+    wsteps = [args.steps // nwin + (wi < args.steps % nwin) for wi in range(nwin)]
     windows = []
-    nwin = max(1, args.windows)
     for wi in range(nwin):
         cdist.barrier()
         torch.cuda.synchronize()
@@ -947,11 +1029,13 @@ def main():
                 TRACE[0], TRACE_T0[0] = [], time.perf_counter()
                 ev0 = torch.cuda.Event(enable_timing=True)
                 ev0.record()
-        run(args.steps, True)
+        run(wsteps[wi], True)
         cdist.barrier()
         torch.cuda.synchronize()
         windows.append(cdist.max_over_ranks(time.perf_counter() - t0, dev))
-    dt = sorted(windows)[len(windows) // 2] if len(windows) % 2 else sorted(windows)[len(windows) // 2 - 1]
+    dt = sum(windows)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(host_arrays(last[0], model.pts_bbox_head.cascade_ratio), args.dump_outputs)
     if args.diag and rank == 0 and TRACE[0]:
         for i, w, a, b, c, ev in sorted(TRACE[0]):
             print("trace: sample %2d stream %d  host: search ready %.1f  issue %.1f -> %.1f ms   GPU done %.1f ms" % (
@@ -1042,10 +1126,11 @@ def main():
                 unit="samples/s", n_gpus=world, world_size_seen_by_backend=seen_world, backend=backend_name, steps=args.steps,
                 warmup=args.warmup,
                 ms_per_step=round(1e3 * dt / args.steps, 3),
-                windows=len(windows), window_ms_per_step=[round(1e3 * w / args.steps, 3) for w in windows],
-                spread_pct=round(100.0 * (max(windows) - min(windows)) / dt, 2),
-                timing=("%d timed windows of %d steps, each bracketed by barrier + torch.cuda.synchronize() (max over ranks); value / "
-                        "ms_per_step = the MEDIAN window" % (len(windows), args.steps)),
+                windows=len(windows), window_ms_per_step=[round(1e3 * w / n, 3) for w, n in zip(windows, wsteps)],
+                spread_pct=round(100.0 * (max(w / n for w, n in zip(windows, wsteps)) - min(w / n for w, n in zip(windows, wsteps)))
+                                 / (dt / args.steps), 2),
+                timing=("%d timed steps in %d window(s) of %s steps, each bracketed by barrier + torch.cuda.synchronize() (max over "
+                        "ranks); value / ms_per_step = all timed steps" % (args.steps, len(windows), "/".join(map(str, wsteps)))),
                 higher_is_better=True, scaling=("strong" if SHARD[0] else "weak"), vs_baseline=None,
                 dtype=("f32 (split-f16 products, fp32 accumulate)" if (args.dtype == "f32" and core.CONV_ENGINE == "h2") else args.dtype),
                 data="synthetic",
@@ -1106,7 +1191,7 @@ def also_line(cfg, dev):
     try:
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "10", "--warmup", "3", "--windows", "2",
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "20", "--warmup", "3", "--windows", "2",
                "--no-cpu-baseline", "--no-kernel-timing", "--also", "none"]
         t0 = time.perf_counter()
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=180)

@@ -101,16 +101,17 @@ def test_pin_rank_threads_gives_every_rank_its_own_cores():
         pytest.skip("no affinity call on this platform")
     before = sorted(os.sched_getaffinity(0))
     try:
-        seen = []
-        for r in range(2):
-            os.sched_setaffinity(0, before)
-            mine = cdist.pin_rank_threads(r, 2)
-            assert mine and set(mine) <= set(before)
-            if len(before) >= 2:
-                assert sorted(os.sched_getaffinity(0)) == mine and len(mine) == len(before) // 2
-            seen.append(set(mine))
-        if len(before) >= 2:
-            assert not (seen[0] & seen[1])
+        for n in (2, 8):
+            seen = []
+            for r in range(n):
+                os.sched_setaffinity(0, before)
+                mine = cdist.pin_rank_threads(r, n)
+                assert mine and set(mine) <= set(before)
+                if len(before) >= n:
+                    assert sorted(os.sched_getaffinity(0)) == mine and len(mine) == len(before) // n
+                seen.append(set(mine))
+            if len(before) >= n:
+                assert all(not (seen[i] & seen[j]) for i in range(n) for j in range(i))
         os.sched_setaffinity(0, before)
         assert cdist.pin_rank_threads(0, 1) == before            # a single rank keeps everything
     finally:
@@ -212,6 +213,37 @@ def test_bench_ticket_orders_collectives_across_threads():
     assert gates.wait_for(-1) is None
     gates.post(0, "ev0")
     assert gates.wait_for(0) == "ev0"
+
+
+def test_bench_dump_outputs_dtypes_cap_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: every array of a step's result lands as float32 / float64, a ``Rows`` volume as its C channels, the
+    capacity-sized fine outputs of the captured dense stage cut to their count; the byte cap holds, and an array over its share is
+    the same sample in every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    rows = torch.randn(8, 5, generator=g)
+    out = dict(pred_c=torch.randn(1, 3, 4, 4, 2, generator=g).half(), depth=torch.arange(5, dtype=torch.float64),
+               big=torch.randn(4096, generator=g), voxel_feats=core.Rows(rows, 1, 2, 2, 2, 3, coff=1), pred_f=None,
+               fine_count=torch.tensor(2, dtype=torch.int32), output_voxels_fine=[torch.randn(100, 3, generator=g)],
+               output_coords_fine=[torch.arange(300, dtype=torch.int32)], SC_metric=np.array([[1, 2], [3, 4]]))
+    arrs = bench.host_arrays(out, cascade_ratio=2)
+    assert set(arrs) == {"pred_c", "depth", "big", "voxel_feats", "fine_count", "output_voxels_fine.0", "output_coords_fine.0", "SC_metric"}
+    assert arrs["pred_c"].dtype == np.float32 and arrs["depth"].dtype == np.float64 and arrs["SC_metric"].dtype == np.float64
+    assert np.array_equal(arrs["voxel_feats"], rows[:, 1:4].numpy())
+    assert arrs["output_voxels_fine.0"].shape == (16, 3) and np.array_equal(arrs["output_coords_fine.0"], np.arange(48.0).reshape(3, 16))
+    limit = 8000
+    for d in ("a", "b"):
+        bench.dump_outputs(arrs, str(tmp_path / d), limit=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrs) and files == sorted(os.listdir(tmp_path / "b"))
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in got.values()) <= limit and all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["pred_c.npy"], arrs["pred_c"])                         # small arrays in full, shape kept
+    big = got["big.npy"]
+    assert 0 < big.size < 4096 and np.isin(big, arrs["big"]).all()
+    for f in files:
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f)), f
 
 
 def test_detector_pickles_and_keeps_its_hooks():

@@ -8,7 +8,6 @@ it costs.
                                                       #     an event record after every replay)
 """
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")       # as bench.py: before HIP starts
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,4 @@
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import bench

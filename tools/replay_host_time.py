@@ -1,6 +1,5 @@
 """Host time of one hipGraphLaunch of the dense stage (136 kernel nodes): is the issuing thread the limit of the pipeline?"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench

@@ -8,7 +8,6 @@
                     prequeue -- every search is dispatched and finished before the first replay is issued (host-side ordering)
 """
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
