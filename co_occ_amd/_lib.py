@@ -173,6 +173,7 @@ SIGNATURES = {
     "coocc_bn_backward_dx": (I, [P, P, P, I, I, P, P, P, F, I, P, P, ctypes.c_double, P, P, P]),
     "coocc_predict_labels": (I, [P, L, L, L, L, I, I, I, I, I, I, I, P, P]),
     "coocc_eval_semantic": (I, [P, L, L, L, L, I, I, I, I, P, P, I, I, I, I, I, P, P]),
+    "coocc_lidarseg_points": (I, [P, L, L, L, L, I, I, I, I, P, L, L, I, I, P, I, I, P, P, I, P, P]),
 }
 
 _lib = None

@@ -1,10 +1,12 @@
-"""Prediction dump of the nuScenes test loop -- mirror of ``save_output_nuscenes`` (P/coocc/apis/utils.py:54-110) and of the
+"""Prediction dump of the nuScenes test loop -- mirror of ``save_output_nuscenes`` (P/coocc/apis/utils.py:54-110), of the lidarseg
+submission writer ``save_nuscenes_lidarseg_submission`` (:112-133) and of the
 label preparation in ``custom_single_gpu_test`` (P/coocc/apis/test.py:67-68,197-201).
 
 Upstream resamples the logits to the ground-truth grid with ``F.interpolate``, takes ``argmax`` on the device, copies an
 int64 volume to the host and narrows it to uint8 there.  ``predict_labels`` produces the uint8 volume on the device in one
 kernel (no resampled [1,C,H,W,D] temporary: 174 MB at 17 x 200 x 200 x 16 fp32); the pickle written by
 ``save_output_nuscenes`` has the upstream keys (``pred_voxels``, ``cam2lidar``, ``img_canvas``)."""
+import json
 import os
 import pickle
 
@@ -58,17 +60,35 @@ def save_output_nuscenes(img_inputs, output_voxels, save_path, scene_token, samp
     return filepath
 
 
+def save_nuscenes_lidarseg_submission(output_points, save_path, img_metas):
+    """P/coocc/apis/utils.py:112-133: ``<save_path>/test/submission.json`` (the upstream ``meta`` dict, written once) and
+    ``<save_path>/lidarseg/test/<lidar_token>_lidarseg.bin``, the point labels as uint8.  ``output_points``: ``simple_test``'s
+    int64 labels (device or host).  Returns the path of the .bin file."""
+    meta_file = os.path.join(save_path, 'test', 'submission.json')
+    if not os.path.exists(meta_file):
+        os.makedirs(os.path.join(save_path, 'test'), exist_ok=True)
+        meta = dict(meta=dict(use_lidar=False, use_camera=True, use_radar=False, use_map=False, use_external=False))
+        with open(meta_file, 'w') as f:
+            json.dump(meta, f)
+    save_path = os.path.join(save_path, 'lidarseg', 'test')
+    os.makedirs(save_path, exist_ok=True)
+    save_file = os.path.join(save_path, '{}_lidarseg.bin'.format(img_metas['lidar_token']))
+    labels = output_points.detach().cpu().numpy() if torch.is_tensor(output_points) else np.asarray(output_points)
+    labels.astype(np.uint8).tofile(save_file)
+    return save_file
+
+
 def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=None):
     """The loop of ``custom_single_gpu_test`` (P/coocc/apis/test.py:43-45: ``result = model(return_loss=False, **data)`` once per
     sample) with ``slots`` samples in flight (``co_occ_amd.serving``): a generator of ``(data, result)`` in sample order, ``result``
     = what ``COOCC_Ray.simple_test`` returns for that sample (same tensors, same metrics, fine outputs trimmed to their exact
     size).  ``data``: the keyword arguments of ``simple_test`` (``img_inputs`` / ``img``, ``points``, ``gt_occ``,
-    ``visible_mask``, ``precomputed``).
+    ``visible_mask``, ``points_occ``, ``img_metas``, ``precomputed``).
 
     Nothing in the loop waits for the sample that was just issued: the encoders upstream of the hot path run eagerly at submit
     time; pooling + index search of the next ``ahead`` samples are prefetched under the dense stages (one captured hipGraph
-    launch per sample) of the current ones; a sample's SC / SSC confusion matrices (``coocc_eval_semantic``) and its fine-point
-    count are computed on ITS dense stream right behind the replay and copied to pinned host memory asynchronously; the sample
+    launch per sample) of the current ones; a sample's SC / SSC confusion matrices (``coocc_eval_semantic``), its lidarseg labels
+    and 16x16 matrix (``coocc_lidarseg_points``, when it carries ``points_occ``) and its fine-point count are computed on ITS dense stream right behind the replay and copied to pinned host memory asynchronously; the sample
     is yielded ``dense_streams`` issues later, when that copy has normally long finished.  A sample whose ``gt_occ`` is not the
     captured fine grid (cascade_ratio x the coarse grid) takes ``model.simple_test`` (eager decode) in its turn.  Result tensors
     of a sample stay valid until ``slots`` more samples have been submitted: consume (or clone) them inside the loop body, as
@@ -88,7 +108,7 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
             return (data, None, res, None)
         out = t.result(wait=False)
         ds = pipe.dense_streams[t.slot % pipe.ndense]
-        gt, vm = data.get("gt_occ"), data.get("visible_mask")
+        gt, vm, po = data.get("gt_occ"), data.get("visible_mask"), data.get("points_occ")
         with torch.cuda.stream(ds):
             parts = []
             if gt is not None:
@@ -97,6 +117,15 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
                     vm.record_stream(ds)
                 both = model._metrics_launch(out, gt, vm)
                 parts.append(both.reshape(-1))
+            lseg = None
+            if po:
+                # the lidarseg labels + 16x16 matrix read the slot's pred_c: here, before the slot can be reused
+                for p in po:
+                    if p.is_cuda:
+                        p.record_stream(ds)
+                lseg = model._lidarseg_launch(out, po, data.get("img_metas"))
+                if not model.metrics_on_device:
+                    parts.append(lseg[1].reshape(-1))
             if out.get("fine_count") is not None:
                 parts.append(out["fine_count"].reshape(-1).to(torch.int64))
             host = ev = None
@@ -107,25 +136,27 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
             from . import streams as cstreams
             ev = cstreams.new_event()           # fires after the pinned-host copy above: a copy command, complete when it does
             ev.record(ds)
-        return (data, t, (out, host, both if gt is not None else None), ev)
+        return (data, t, (out, host, both if gt is not None else None, lseg), ev)
 
     def finish(item):
         data, t, payload, ev = item
         if t is None:
             return data, payload
-        out, host, both = payload
+        out, host, both, lseg = payload
         ev.synchronize()
         from . import core
         core.check_h2_overflow()
         out = dict(out)
         gt, vm = data.get("gt_occ"), data.get("visible_mask")
         C = ncls_of(out)
-        nm = 0
+        nm = nl = 0                               # host buffer: [ metrics (nm) | lidarseg matrix (nl) | fine count ]
         if gt is not None:
             nm = both.numel()
+        if lseg is not None and not model.metrics_on_device:
+            nl = lseg[1].numel()
         if out.get("fine_count") is not None and out.get("output_voxels_fine") is not None and not t.fallback:
             cf = model.pts_bbox_head.cascade_ratio
-            n = int(host[nm]) * cf ** 3
+            n = int(host[nm + nl]) * cf ** 3
             # capacity-sized fine outputs of the captured form -> the exact-size tensors simple_test returns (views of the
             # slot's static buffers: no copy; the device-count kernels pack [3][n] at the start of the coords buffer)
             out["output_voxels_fine"] = [out["output_voxels_fine"][0][:n]]
@@ -134,6 +165,9 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
         if gt is not None:
             m = both if model.metrics_on_device else host[:nm].numpy().reshape(both.shape).copy()
             out.update(model._metrics_finish(m, C, vm is not None))
+        if lseg is not None:
+            hist = lseg[1] if model.metrics_on_device else host[nm:nm + nl].numpy().copy()
+            out.update(model._lidarseg_finish(lseg[0], hist, data["points_occ"]))
         return data, out
 
     try:

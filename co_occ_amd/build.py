@@ -14,7 +14,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # multiplies with op_sel swaps -- among them the form gfx950 mis-reads beside 128-bit-operand MFMAs.  Compiling the
 # whole kernel COOCC_SCALAR_FP32 instead put a 96-float accumulator array into scratch (openocc 82 -> 53 samples/s); without SLP
 # the explicit f32x4 math stays packed and the form is gone (tools/isa_lint.py checks the result either way).
-FILE_FLAGS = {"fine_fused.hip": ["-fno-slp-vectorize"]}
+# lidarseg.hip: the trilinear point sampler restates ATen's CPU grid_sampler_3d operation by operation so the sampled logits are the
+# CPU's bits; a contracted multiply-add would round once where the CPU rounds twice.
+FILE_FLAGS = {"fine_fused.hip": ["-fno-slp-vectorize"], "lidarseg.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -470,9 +470,10 @@ class COOCC_Ray(nn.Module):
         post_rots, post_trans, bda, ...); ``points`` = [points [N,5]].  ``precomputed=dict(img_voxel_feats= | depth= + ctx=,
         pts_voxel_feats=, gemo=, img_feats=)`` (an extension) bypasses the upstream encoders.
         In eval mode the dense stage runs as one captured hipGraph launch (``graph_simple_test``; same bits as the eager
-        launches, which remain the fallback for configurations / frames the captured form does not cover)."""
-        if points_occ is not None:
-            raise NotImplementedError("lidarseg evaluation (forward_lidarseg) is not on the hot path")
+        launches, which remain the fallback for configurations / frames the captured form does not cover).
+        ``points_occ`` ([points [N,>=4]], label in column 3; ``gt_occ`` may be None, the test-submission case) adds the lidarseg
+        keys of coocc_ray.py:556-560, 648-651: ``output_points`` (int64 labels 1..16 on the device), ``target_points`` and
+        ``evaluation_semantic`` (16x16 int64; a device tensor under ``metrics_on_device``)."""
         fine_size = list(gt_occ.shape[1:]) if gt_occ is not None else None
         out = None
         lifted = precomputed is not None and precomputed.get("depth") is not None
@@ -496,19 +497,35 @@ class COOCC_Ray(nn.Module):
             voxel_feats, img_feats, _, _, gemo, _ = self.extract_feat(points, img=img, img_metas=img_metas)
             transform = img[1:] if img is not None else None
             out = self.decode(voxel_feats, gemo, img_feats, transform, fine_size=fine_size)
-        return self.finish_test_result(out, gt_occ, visible_mask)
+        return self.finish_test_result(out, gt_occ, visible_mask, points_occ=points_occ, img_metas=img_metas)
 
-    def finish_test_result(self, out, gt_occ=None, visible_mask=None):
+    def finish_test_result(self, out, gt_occ=None, visible_mask=None, points_occ=None, img_metas=None):
         """The tail of ``simple_test`` (coocc_ray.py:539-560, 629-656) on a decoded sample: the reference's result keys and,
-        with ground truth, the SC / SSC confusion matrices."""
+        with ground truth, the SC / SSC confusion matrices; with ``points_occ``, the lidarseg keys."""
         out = dict(out)
         out.update(output_voxels=out["pred_c"], target_voxels=gt_occ)
+        lseg = self._lidarseg_launch(out, points_occ, img_metas) if points_occ else None
         if gt_occ is not None:
             out.update(self._metrics(out, gt_occ, visible_mask))
-            if not self.metrics_on_device:
-                from . import core
-                core.check_h2_overflow()      # the metrics were read back: the whole sample has finished on this stream
+        if lseg is not None:
+            labels, hist = lseg
+            out.update(self._lidarseg_finish(labels, hist if self.metrics_on_device else hist.cpu().numpy(), points_occ))
+        if (gt_occ is not None or lseg is not None) and not self.metrics_on_device:
+            from . import core
+            core.check_h2_overflow()          # the metrics were read back: the whole sample has finished on this stream
         return out
+
+    def _lidarseg_launch(self, out, points_occ, img_metas=None):
+        """coocc_ray.py:556-560 on the device: the eval labels of ``forward_lidarseg`` (argmax of the softmax over classes
+        1..16, + 1) and the 16x16 ``simple_evaluation_semantic`` matrix of pred_c at the points, one kernel per batch element on
+        the CURRENT stream -> (int64 [N], int64 [16,16]).  No synchronisation."""
+        return self.pts_bbox_head.lidarseg_labels(out["pred_c"], points_occ, img_metas)
+
+    @staticmethod
+    def _lidarseg_finish(labels, hist, points_occ):
+        """The result keys of coocc_ray.py:648-651; ``hist``: the host matrix (numpy) or the device tensor (``metrics_on_device``)."""
+        return dict(output_points=labels, target_points=torch.cat(list(points_occ), dim=0),
+                    evaluation_semantic=hist.reshape(16, 16))
 
     def evaluation_semantic(self, pred, gt, eval_type, visible_mask=None):
         """coocc_ray.py:659-684 on the device (no .cpu().numpy())."""
@@ -522,9 +539,9 @@ class COOCC_Ray(nn.Module):
         the OccHead losses ``loss_voxel_{ce,sem_scal,geo_scal,lovasz}_{c_0,fine}`` (co_occ_amd.losses), ``loss_norm``
         rescaling, and the render regulariser ``loss_depth_render`` / ``loss_rgb`` (camera branch :358-434) or
         ``loss_depth_render`` alone through ``get_frustum`` (LiDAR-only branch :436-496).  Everything between the
-        encoders and the losses is an autograd Function over the HIP kernels (``forward_train_hot_path``)."""
-        if points_occ is not None:
-            raise NotImplementedError("lidarseg supervision (forward_lidarseg) is not on the hot path")
+        encoders and the losses is an autograd Function over the HIP kernels (``forward_train_hot_path``).  ``points_occ``
+        ([points [N,>=4]], label in the last column) adds ``point_mean_iou`` (OccHead.loss, occ_head.py:333-335): a float64
+        device tensor, no host read."""
         depth = None
         if precomputed is not None:
             img_voxel_feats, pts_voxel_feats = precomputed.get("img_voxel_feats"), precomputed.get("pts_voxel_feats")
@@ -551,7 +568,7 @@ class COOCC_Ray(nn.Module):
         fine = [res["fine_logits"]] if "fine_logits" in res else None
         coords = [res["fine_xyz"]] if "fine_xyz" in res else None
         losses.update(head.loss(output_voxels=[logits], output_voxels_fine=fine, output_coords_fine=coords,
-                                target_voxels=gt_occ, visible_mask=visible_mask))
+                                target_voxels=gt_occ, target_points=points_occ, img_metas=img_metas, visible_mask=visible_mask))
         if self.loss_norm:                                     # :351-354
             for k in list(losses):
                 if k.startswith('loss'):

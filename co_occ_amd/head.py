@@ -451,8 +451,6 @@ class OccHead(nn.Module):
     def forward(self, voxel_feats, img_feats=None, img_metas=None, pts_feats=None, target_points=None,
                 transform=None, points=None, **kwargs):
         assert type(voxel_feats) is list and len(voxel_feats) == self.num_level
-        if target_points:
-            raise NotImplementedError("forward_lidarseg is not on the hot path")
         if self.training:
             return self._forward_train(voxel_feats, img_feats, transform, kwargs.get("generator"))
         ovf, occ = self.forward_coarse_rows(voxel_feats)
@@ -466,8 +464,60 @@ class OccHead(nn.Module):
             else:
                 fine, xyz = self._fine(ovf, occ, img_feats, transform, image_branch=kwargs.get("image_branch"))
             res['output_voxels_fine'], res['output_coords_fine'] = [fine], [xyz]
+        if target_points:                                   # occ_head.py:246-253
+            res['output_points'] = self.forward_lidarseg(res['output_voxels'][0], target_points, img_metas)
         self.last_out_voxel_feats = ovf
         return res
+
+    # ---------------------------------------------------------------- lidarseg (occ_head.py:339-383)
+    def lidarseg_range(self, img_metas=None):
+        """``img_metas[0]['pc_range']`` as the reference reads it; when the metas do not carry it (an extension), the head's own
+        ``point_cloud_range``."""
+        if img_metas and isinstance(img_metas[0], dict) and 'pc_range' in img_metas[0]:
+            return [float(v) for v in img_metas[0]['pc_range']]
+        return self.point_cloud_range.tolist()
+
+    def forward_lidarseg(self, output_voxels, points, img_metas=None):
+        """occ_head.py:339-383: ``output_voxels`` [B,C,X,Y,Z] logits (any strides), ``points`` one [N_b,>=4] tensor per batch
+        element.  Each point samples the logits trilinearly (grid_sample, align_corners=True, ``self.padding_mode``; points
+        outside the range are kept, as upstream).  Eval: the softmax [sum N_b, C].  Train: ``{'point_mean_iou': float64 0-dim
+        device tensor}``, the nanmean IoU of the 16x16 ``fast_hist_crop`` matrix of argmax(logits[:, 1:]) + 1 against the last
+        point column -- computed on the device, no host read.  One ``coocc_lidarseg_points`` launch per batch element."""
+        from . import evaluation as E
+        B, C = output_voxels.shape[:2]
+        assert len(points) == B, "one point tensor per batch element"
+        logits = output_voxels.detach().float()
+        rng = self.lidarseg_range(img_metas)
+        if self.training:
+            hist = torch.empty(E.LIDARSEG_CLASSES ** 2, dtype=_I64, device=logits.device)
+            for b, p in enumerate(points):
+                E.lidarseg_points(logits[b], p, rng, self.padding_mode, train=True, hist=hist, accumulate=b > 0)
+            return {'point_mean_iou': E.point_mean_iou(hist.view(E.LIDARSEG_CLASSES, E.LIDARSEG_CLASSES))}
+        n = [int(p.shape[0]) for p in points]
+        probs = torch.empty(sum(n), C, dtype=_F32, device=logits.device)
+        o = 0
+        for b, p in enumerate(points):
+            E.lidarseg_points(logits[b], p, rng, self.padding_mode, probs=probs[o:o + n[b]])
+            o += n[b]
+        return probs
+
+    def lidarseg_labels(self, output_voxels, points, img_metas=None):
+        """The eval labels and the evaluation matrix of ``COOCC_Ray.simple_test`` (coocc_ray.py:556-560, 693-700) straight from
+        the logits: argmax over classes 1..16 of the ``forward_lidarseg`` softmax + 1 -> int64 [sum N_b], and ``fast_hist_crop``
+        against ``int(points[:, 3])`` -> int64 [16,16]; both on the device, one launch per batch element, no probabilities."""
+        from . import evaluation as E
+        B = output_voxels.shape[0]
+        assert len(points) == B, "one point tensor per batch element"
+        logits = output_voxels.detach().float()
+        rng = self.lidarseg_range(img_metas)
+        n = [int(p.shape[0]) for p in points]
+        labels = torch.empty(sum(n), dtype=_I64, device=logits.device)
+        hist = torch.empty(E.LIDARSEG_CLASSES ** 2, dtype=_I64, device=logits.device)
+        o = 0
+        for b, p in enumerate(points):
+            E.lidarseg_points(logits[b], p, rng, self.padding_mode, labels=labels[o:o + n[b]], hist=hist, accumulate=b > 0)
+            o += n[b]
+        return labels, hist.view(E.LIDARSEG_CLASSES, E.LIDARSEG_CLASSES)
 
     def _note_fine(self, rec):
         """Remember what ``scatter_fine`` needs for the fine points a ``_fine`` call produced, keyed by the address of their
@@ -531,8 +581,6 @@ class OccHead(nn.Module):
     def loss(self, output_voxels=None, output_coords_fine=None, output_voxels_fine=None, target_voxels=None,
              target_points=None, img_metas=None, visible_mask=None, **kwargs):
         """occ_head.py:312-337."""
-        if target_points:
-            raise NotImplementedError("forward_lidarseg is not on the hot path")
         loss_dict = {}
         for index, ov in enumerate(output_voxels):
             loss_dict.update(self.loss_voxel(ov, target_voxels, tag='c_%d' % index))
@@ -543,4 +591,6 @@ class OccHead(nn.Module):
                     acc[k] = acc[k] + v if k in acc else v
             for k, v in acc.items():
                 loss_dict[k] = v / len(output_coords_fine)
+        if target_points:                                   # :333-335
+            loss_dict.update(self.forward_lidarseg(output_voxels[0], target_points, img_metas))
         return loss_dict

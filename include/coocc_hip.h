@@ -756,6 +756,20 @@ int coocc_predict_labels(const float* pred, int64_t stride_c, int64_t stride_x, 
                          int64_t stride_z, int C, int h, int w, int d, int H, int W, int D, uint8_t* labels,
                          void* stream);
 
+/* LiDAR-segmentation point predictions: OccHead.forward_lidarseg (P/coocc/dense_heads/occ_head.py:339-383) + the label
+ * and histogram steps of COOCC_Ray.simple_test (P/coocc/detectors/coocc_ray.py:556-560, 693-700).  logits: [C,X,Y,Z]
+ * addressed by element strides as in coocc_eval_semantic; points:[n, point_cols] rows of point_stride floats, (x, y, z)
+ * first; range_host:[6] xyz min | xyz max.  Each point is sampled as F.grid_sample(mode='bilinear', align_corners=True)
+ * with padding_mode 1 = border or 0 = zeros (out-of-range points are kept, as upstream); mode 0 = eval (softmax, label =
+ * first maximum of the probabilities over classes 1..C-1, + 1), mode 1 = train (label from the raw sampled logits).
+ * Optional outputs (NULL = not written): probs:[n,C] fp32 (eval only), labels:[n] int64, hist:int64[16*16] =
+ * fast_hist_crop(label, int(trunc(points[:, label_col])), arange(16)) indexed [target-1][label-1] over targets 1..16;
+ * hist needs C == 17; accumulate != 0 adds to it.  2 <= C <= 32. */
+int coocc_lidarseg_points(const float* logits, int64_t stride_c, int64_t stride_x, int64_t stride_y, int64_t stride_z,
+                          int C, int X, int Y, int Z, const float* points, int64_t n, int64_t point_stride, int point_cols,
+                          int label_col, const float* range_host, int padding_mode, int mode, float* probs, int64_t* labels,
+                          int accumulate, int64_t* hist, void* stream);
+
 /* ---------------------------------------------------------------- LiDAR producer */
 /* Hard voxelisation (mmdet3d/ops/voxel/src/voxelization_cpu.cpp:44-104 = the deterministic CUDA path of
  * voxelization_cuda.cu): points:[n,F] (xyz first); range_host:[6] xyzxyz min/max; voxel_size_host:[3].
