@@ -333,9 +333,9 @@ class DevPtr(ctypes.c_void_p):
     while later arguments of the same call are still being built."""
 
 
-def ptr(t, dtype=None, strided=False):
-    """Device pointer of a contiguous HIP tensor (None -> NULL).  ``strided=True`` is for entry points that
-    take element strides explicitly."""
+def ptr(t, dtype=None, strided=False, offset=0):
+    """Device pointer of a contiguous HIP tensor (None -> NULL), ``offset`` elements past its first.  ``strided=True`` is
+    for entry points that take element strides explicitly."""
     if t is None:
         return c_void_p(0)
     if not t.is_cuda:
@@ -344,7 +344,7 @@ def ptr(t, dtype=None, strided=False):
         raise CooccError("expected %s, got %s" % (dtype, t.dtype))
     if not strided and not t.is_contiguous():
         raise CooccError("tensor must be contiguous")
-    p = DevPtr(t.data_ptr())
+    p = DevPtr(t.data_ptr() + offset * t.element_size())
     p._keep = t
     return p
 

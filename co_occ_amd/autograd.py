@@ -11,8 +11,8 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, call, ptr
-from .core import TILE_HINT, out_dim, workspace
+from ._lib import call, ptr
+from .core import TILE_HINT, conv_desc, launch_conv, out_dim, workspace, ztrim_range
 
 _F32 = torch.float32
 _tables = {}
@@ -48,11 +48,6 @@ def _amax_word(dev):
         _amax_words[key] = torch.zeros(2048, device=dev, dtype=torch.int32)
     return _amax_words[key]
 
-
-def _second_word(t):
-    p = _lib.DevPtr(t.data_ptr() + 4)
-    p._keep = t
-    return p
 
 def _pad4(n):
     return (n + 3) // 4 * 4
@@ -248,7 +243,7 @@ def _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw, gscale=None):
         call("coocc_wino_operand_kh2", 0, ptr(x2d), x2d.shape[1], B, X, Y, Z, Cin, tile, ptr(Vk), G, vs, None)
         call("coocc_wino_operand_kh2", 1, ptr(dacc), dacc.shape[1], B, X, Y, Z, Cout, tile, ptr(Mk), G, ms, ptr(gscale))
         with _lib.TIMER.region("k_wgrad_h2 wino%d" % tile, 2.0 * pts * rows * 3 * Cin * Cout):
-            call("coocc_wino_wgrad_h2", ptr(Vk), ptr(Mk), G, Z, Cin, Cout, tile, 1.0 / (vs * ms), _second_word(gscale), ptr(dw), 0,
+            call("coocc_wino_wgrad_h2", ptr(Vk), ptr(Mk), G, Z, Cin, Cout, tile, 1.0 / (vs * ms), ptr(gscale, offset=1), ptr(dw), 0,
                  ptr(ws), ws.numel())
         return True
     V = core._wino_buffer(dev, "V", pts * G * Cin)
@@ -268,40 +263,21 @@ def _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw, gscale=None):
     return True
 
 
-def _zrange(Zin, Zout, stride, pad):
-    """First / last z tap of a 3-tap axis that reads a real voxel for at least one output (thin grids: Z = 1, 2)."""
-    ok = [kz for kz in range(3) if any(0 <= zo * stride - pad + kz < Zin for zo in range(Zout))]
-    return ok[0], ok[-1]
-
-
 def _conv_launch(x2d, in_C, w_packed, out2d, Cout, taps, geom_in, geom_out, ksize, stride, pad, scale, shift, res2d, relu,
                  table=None, tag="conv_fwd", out_rows=None, kdims=None, h2_alpha=None, alpha_dev=None):
     """``h2_alpha``: x2d holds H2 rows (coocc_rows_to_h2, operand scale 1 / h2_alpha) and w_packed an H2 pack: split-f16 engine;
     ``alpha_dev``: device word the accumulators are also multiplied by (the inverse of a device-chosen operand scale)."""
-    d = ConvDesc()
-    ws = workspace(x2d.device)
-    d.in_, d.w, d.out = ptr(x2d), ptr(w_packed), ptr(out2d)
-    d.scale, d.bias = ptr(scale), ptr(shift)
-    d.res = ptr(res2d)
-    d.gather = ptr(table, torch.int32) if table is not None else None
-    d.out_rows = ptr(out_rows, torch.int32) if out_rows is not None else None
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = (out_rows.shape[0] if out_rows is not None else out2d.shape[0]), in_C, Cout, taps
-    d.in_stride, d.out_stride = x2d.shape[1], out2d.shape[1]
-    d.res_stride = res2d.shape[1] if res2d is not None else 0
-    B, Xi, Yi, Zi = geom_in
-    _, Xo, Yo, Zo = geom_out
-    d.B, d.Xi, d.Yi, d.Zi, d.Xo, d.Yo, d.Zo = B, Xi, Yi, Zi, Xo, Yo, Zo
-    d.ksize, d.stride, d.pad = ksize, stride, pad
+    M = out_rows.shape[0] if out_rows is not None else out2d.shape[0]
+    d = conv_desc(x2d.device, in_=ptr(x2d), w=ptr(w_packed), out=ptr(out2d), scale=ptr(scale), bias=ptr(shift), res=ptr(res2d),
+                  gather=ptr(table, torch.int32), out_rows=ptr(out_rows, torch.int32), M=M, Cin=in_C, Cout=Cout, taps=taps,
+                  in_stride=x2d.shape[1], out_stride=out2d.shape[1], res_stride=res2d.shape[1] if res2d is not None else 0,
+                  B=geom_in[0], Xi=geom_in[1], Yi=geom_in[2], Zi=geom_in[3], Xo=geom_out[1], Yo=geom_out[2], Zo=geom_out[3],
+                  ksize=ksize, stride=stride, pad=pad, relu=int(relu), res_mode=1 if res2d is not None else 0, tile_hint=TILE_HINT)
     if kdims is not None:
         d.kx, d.ky, d.kz, d.px, d.py, d.pz = kdims
-    d.relu, d.res_mode, d.splitk = int(relu), (1 if res2d is not None else 0), 0
-    d.tile_hint = TILE_HINT
     if h2_alpha is not None:
-        d.in_stride, d.mfma_dtype, d.alpha, tag = in_C, 3, float(h2_alpha), "k_gemm_h2 " + tag
-        d.alpha_dev = alpha_dev
-    with _lib.TIMER.region(tag, 2.0 * d.M * in_C * Cout * taps):
-        _lib.conv_fwd(d, x2d.device)
+        d.in_stride, d.mfma_dtype, d.alpha, d.alpha_dev, tag = in_C, 3, float(h2_alpha), alpha_dev, "k_gemm_h2 " + tag
+    launch_conv(d, x2d.device, tag, 2.0 * M * in_C * Cout * taps)
 
 
 class ConvRowsFn(torch.autograd.Function):
@@ -326,7 +302,7 @@ class ConvRowsFn(torch.autograd.Function):
                 _wino_train(x2d, geom, w_.view(Cout, Cin, 3, 3, 3), False, out, scale, eff_shift, res2d, relu)):
             kd, wsub, nt = None, w_.reshape(Cout, Cin, taps), taps
             if ksize == 3:
-                lo, hi = _zrange(Zi, Zo, stride, pad)
+                lo, hi = ztrim_range(Zi, Zo, stride, pad)
                 if hi - lo < 2:         # z taps that only read padding are dropped (exact)
                     wsub = w_.view(Cout, Cin, 3, 3, 3)[..., lo:hi + 1].contiguous().view(Cout, Cin, -1)
                     nt, kd = wsub.shape[2], (3, 3, hi - lo + 1, pad, pad, pad - lo)
@@ -380,7 +356,7 @@ class ConvRowsFn(torch.autograd.Function):
             elif stride == 1:
                 kd, wsub, nt, pd = None, w3, taps, ksize - 1 - pad
                 if ksize == 3:
-                    lo, hi = _zrange(geom_out[3], Zi, 1, pd)        # z taps of the flipped kernel that see real dy voxels
+                    lo, hi = ztrim_range(geom_out[3], Zi, 1, pd)        # z taps of the flipped kernel that see real dy voxels
                     if hi - lo < 2:
                         wsub = weight.detach().float().view(Cout, Cin, 3, 3, 3)[..., 2 - hi:2 - lo + 1].contiguous().view(Cout, Cin, -1)
                         nt, kd = wsub.shape[2], (3, 3, hi - lo + 1, pd, pd, pd - lo)
@@ -388,7 +364,7 @@ class ConvRowsFn(torch.autograd.Function):
                     # the gradient operand scaled by gscale[0] (chosen on the device), undone by the GEMM through gscale[1]
                     _conv_launch(_rows_h2(dacc, Cout, gscale_d), Cout, pack_weights_h2_dev(wsub, Cout, Cin, nt, 2), dx, Cin,
                                  nt, geom_out, geom, ksize, 1, pd, None, None, None, False, tag="conv_dgrad", kdims=kd,
-                                 h2_alpha=1.0, alpha_dev=_second_word(gscale_d))
+                                 h2_alpha=1.0, alpha_dev=ptr(gscale_d, offset=1))
                 else:
                     wp = pack_weights_dev(wsub, Cout, Cin, nt, 2)
                     _conv_launch(dacc, Cp, wp, dx, Cin, nt, geom_out, geom, ksize, 1, pd, None, None, None, False,
@@ -411,7 +387,7 @@ class ConvRowsFn(torch.autograd.Function):
                 xk = _kh2(x2d, Mi, Mp, Cin, 1.0, None, torch.empty(Mp * Cin, device=dev, dtype=_F32))
                 dk = _kh2(dacc, Mo, Mp, Cout, 1.0, gscale, torch.empty(Mp * Cout, device=dev, dtype=_F32))
                 with _lib.TIMER.region("k_wgrad_h2", 2.0 * Mo * Cin * Cout):
-                    call("coocc_conv_wgrad_h2", ptr(xk), ptr(dk), Mp, Cin, Cout, 1.0, _second_word(gscale), ptr(dw), 0, ptr(ws),
+                    call("coocc_conv_wgrad_h2", ptr(xk), ptr(dk), Mp, Cin, Cout, 1.0, ptr(gscale, offset=1), ptr(dw), 0, ptr(ws),
                          ws.numel())
             else:
                 tb = tap_table(dev, B, Xi, Yi, Zi, ksize, stride, pad, False) if (taps > 1 or stride > 1) else None

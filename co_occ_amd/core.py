@@ -112,12 +112,17 @@ def branch_streams_of(device, stream):
     return [s for (d, h, _), s in _branch_streams.items() if d == device.index and h == stream.cuda_stream]
 
 
-def conv_kernel_name(M, Cout, table, hint=0, iters=1 << 30, one_by_one=False):
+def conv_kernel_name(M, Cout, table, hint=0, iters=1 << 30, one_by_one=False, grouped=False):
     """Mirror of the tile-configuration rule in csrc/conv3d.hip (coocc_conv_fwd).  iters = taps * ceil(Cin/32);
-    one_by_one: a 1x1x1 stride-1 layer (takes the persistent kernel when it has more than 768 tiles)."""
+    one_by_one: a 1x1x1 stride-1 layer (takes the persistent kernel when it has more than 768 tiles);
+    grouped: a launch with one weight set per row group (the Winograd GEMM: persistent workgroups, >= 2 tiles each, where
+    it would take k_conv2<128> with more than 768 tiles)."""
     if (one_by_one and CONV_PERSIST and CONV_V2 and not table and Cout > 64 and M >= 8192 and iters <= 24
             and -(-M // 128) * -(-Cout // 128) > 768):
         return "k_conv2p<1x1>"
+    if (grouped and CONV_PERSIST and CONV_V2 and iters <= 24 and (M // 128) * -(-Cout // 128) > 768
+            and conv_kernel_name(M, Cout, table, hint, iters) == "k_conv2<128>"):
+        return "k_conv2p"
     hint = hint or TILE_HINT
     if Cout <= 32:
         t = "128,32,32,32"
@@ -167,8 +172,8 @@ class Rows:
         return self.X * self.Y * self.Z
 
     def data(self):
-        """ctypes pointer to channel 0 of row 0."""
-        return ctypes.c_void_p(self.t.data_ptr() + 4 * self.coff)
+        """Device pointer to channel 0 of row 0."""
+        return ptr(self.t, offset=self.coff)
 
     def as_ncdhw(self):
         """Reference-layout view [B,C,X,Y,Z] (no copy).  The view remembers these Rows (and the tensor version they were
@@ -533,31 +538,50 @@ def check_h2_overflow(reset=True):
             "(INTEGRATION.md, 'Operand range of the split-f16 engine')." % (32768.0 / (100 * H2_WINO_SCALE[4])))
 
 
+def ztrim_range(Zin, Zout, stride, pad):
+    """First / last z tap of a 3-tap axis that reads a real voxel for at least one output z; on thin grids (Z = 1, 2) the
+    taps outside lo..hi only multiply padding."""
+    ok = [kz for kz in range(3) if any(0 <= zo * stride - pad + kz < Zin for zo in range(Zout))]
+    return ok[0], ok[-1]
+
+
+def _route(B, X, Y, Z, pc, rm, splitk):
+    """``route`` -> (family, Winograd plan or None, z trim (lo, hi) or None, taps after the trim)."""
+    Zo = out_dim(Z, pc.ksize, pc.stride, pc.pad)
+    M = B * out_dim(X, pc.ksize, pc.stride, pc.pad) * out_dim(Y, pc.ksize, pc.stride, pc.pad) * Zo
+    bf16, f16 = CONV_DTYPE == "bf16", CONV_DTYPE == "f16"
+    plan = None if (bf16 or f16) else _wino_plan_geom(B, X, Y, Z, pc, M, rm)
+    if plan is not None:
+        return "wino", plan, None, 3
+    taps, trim = pc.taps, None
+    if ZTRIM and pc._w_cube is not None:
+        lo, hi = ztrim_range(Z, Zo, pc.stride, pc.pad)
+        if hi - lo < 2:
+            taps, trim = 9 * (hi - lo + 1), (lo, hi)
+    if f16 and pc.Cin % 64 == 0 and pc._w_taps is not None and rm in (0, 1) and splitk in (0, 1):
+        return "f16", None, trim, taps
+    if (not bf16 and not f16 and CONV_ENGINE == "h2" and H2_DIRECT and pc.Cin % 32 == 0 and pc._w_taps is not None
+            and rm in (0, 1) and 2.0 * M * pc.Cin * pc.Cout * taps >= H2_DIRECT_MIN_FLOPS):
+        return "h2", None, trim, taps
+    return "other", None, trim, taps
+
+
 def route(B, X, Y, Z, pc, rm=0, splitk=0):
     """Which kernel family ``conv_rows`` takes for layer ``pc`` on an input grid [B, X, Y, Z]: "wino" | "h2" | "f16" | "other".
     One rule for the dispatch itself and for the producers that decide whether to write an H2 twin for their consumer."""
-    Xo, Yo, Zo = out_dim(X, pc.ksize, pc.stride, pc.pad), out_dim(Y, pc.ksize, pc.stride, pc.pad), out_dim(Z, pc.ksize, pc.stride, pc.pad)
-    M = B * Xo * Yo * Zo
-    bf16, f16 = CONV_DTYPE == "bf16", CONV_DTYPE == "f16"
-    if not (bf16 or f16) and _wino_plan_geom(B, X, Y, Z, pc, M, rm) is not None:
-        return "wino"
-    taps = pc.taps
-    if ZTRIM and pc._w_cube is not None:
-        ok = [kz for kz in range(3) if any(0 <= zo * pc.stride - pc.pad + kz < Z for zo in range(Zo))]
-        if ok[-1] - ok[0] + 1 < 3:
-            taps = 9 * (ok[-1] - ok[0] + 1)
-    if f16 and pc.Cin % 64 == 0 and pc._w_taps is not None and rm in (0, 1) and splitk in (0, 1):
-        return "f16"
-    if (not bf16 and not f16 and CONV_ENGINE == "h2" and H2_DIRECT and pc.Cin % 32 == 0 and pc._w_taps is not None
-            and rm in (0, 1) and 2.0 * M * pc.Cin * pc.Cout * taps >= H2_DIRECT_MIN_FLOPS):
-        return "h2"
-    return "other"
+    return _route(B, X, Y, Z, pc, rm, splitk)[0]
 
 
 def takes_h2(rows, consumers):
     """True when one of the layers ``consumers`` (PackedConv or None) reads ``rows`` (a Rows, or a (B, X, Y, Z) grid) as H2 rows."""
     g = (rows.B, rows.X, rows.Y, rows.Z) if isinstance(rows, Rows) else rows
     return any(pc is not None and route(*g, pc) == "h2" for pc in consumers)
+
+
+def wants_h2_twin(rows, consumers):
+    """True when the producer of Rows ``rows`` writes their H2 twin (``rows.h2``): one of the layers ``consumers`` reads them on
+    the split-f16 direct path."""
+    return CONV_ENGINE == "h2" and CONV_DTYPE == "f32" and rows.C % 32 == 0 and takes_h2(rows, consumers)
 
 
 def conv_rows_wino(x, pc, out, relu, res, plan, in_ranges=None, twin=False):
@@ -580,39 +604,25 @@ def conv_rows_wino(x, pc, out, relu, res, plan, in_ranges=None, twin=False):
             assert in_ranges is None or sum(c for _, c in in_ranges) == pc.Cin
             voff = 0
             for coff, cr in (in_ranges or [(0, pc.Cin)]):
-                src = _lib.DevPtr(x.t.data_ptr() + 4 * (x.coff + coff))
-                src._keep = x.t
-                dst = _lib.DevPtr(V.data_ptr() + 4 * voff)        # H2 rows: 128 bytes per 32-channel chunk = 4 bytes per channel too
-                dst._keep = V
+                src = ptr(x.t, offset=x.coff + coff)
+                dst = ptr(V, offset=voff)        # H2 rows: 128 bytes per 32-channel chunk = 4 bytes per channel too
                 if h2:
                     call("coocc_wino_input_h2_ex", src, x.stride, x.B, x.X, x.Y, x.Z, cr, tile, dst, pc.Cin, G, vscale, ptr(sdev))
                 else:
                     call("coocc_wino_input_strided", src, x.stride, x.B, x.X, x.Y, x.Z, cr, tile, dst, pc.Cin, G)
                 voff += cr
-    d = ConvDesc()
-    ws = workspace(dev)
-    d.in_, d.w, d.out = ptr(V), ptr(wp), ptr(Mb)
-    d.scale = d.bias = d.res = d.gather = d.out_rows = None
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = pts * G, pc.Cin, pc.Cout, 3
-    d.in_stride, d.out_stride, d.res_stride = pc.Cin, pc.Cout, 0
-    d.B, d.Xi, d.Yi, d.Zi, d.Xo, d.Yo, d.Zo = pts * G // x.Z, 1, 1, x.Z, 1, 1, x.Z
-    d.ksize, d.stride, d.pad = 3, 1, 1
-    d.kx, d.ky, d.kz, d.px, d.py, d.pz = 1, 1, 3, 0, 0, 1
-    d.wgroup_rows = G
-    d.relu, d.res_mode, d.splitk, d.tile_hint = 0, 0, 1, (hint or TILE_HINT)
-    kname = conv_kernel_name(pts * G, pc.Cout, False, hint, 3 * -(-pc.Cin // 32))
-    if (CONV_PERSIST and CONV_V2 and kname == "k_conv2<128>" and 3 * -(-pc.Cin // 32) <= 24
-            and (pts * G // 128) * -(-pc.Cout // 128) > 768):
-        kname = "k_conv2p"          # mirror of the dispatch in coocc_conv_fwd: persistent workgroups, >= 2 tiles each
+    d = conv_desc(dev, in_=ptr(V), w=ptr(wp), out=ptr(Mb), M=pts * G, Cin=pc.Cin, Cout=pc.Cout, taps=3,
+                  in_stride=pc.Cin, out_stride=pc.Cout, B=pts * G // x.Z, Xi=1, Yi=1, Zi=x.Z, Xo=1, Yo=1, Zo=x.Z,
+                  ksize=3, stride=1, pad=1, kx=1, ky=1, kz=3, pz=1, wgroup_rows=G, splitk=1, tile_hint=hint or TILE_HINT)
+    flops = 2.0 * pts * rows * pc.Cin * pc.Cout * 3
     if h2:
-        d.mfma_dtype, d.alpha, kname = 3, 1.0 / vscale, "k_gemm_h2z"
+        d.mfma_dtype, d.alpha = 3, 1.0 / vscale
         if sdev is not None:
-            inv = _lib.DevPtr(sdev.data_ptr() + 4)
-            inv._keep = sdev
-            d.alpha_dev = inv
-    with TIMER.region(kname + " wino%d" % tile, 2.0 * pts * rows * pc.Cin * pc.Cout * 3):
-        _lib.conv_fwd(d, V.device)
+            d.alpha_dev = ptr(sdev, offset=1)
+        launch_conv(d, V.device, "k_gemm_h2z wino%d" % tile, flops)
+    else:
+        launch_conv(d, V.device, lambda: conv_kernel_name(pts * G, pc.Cout, False, hint, 3 * -(-pc.Cin // 32), grouped=True)
+                    + " wino%d" % tile, flops)
     tw = None
     if twin and h2 and pc.Cout % 32 == 0 and out.coff == 0 and out.stride % 4 == 0:
         tw = out.h2 = torch.empty(out.B * out.V, pc.Cout, device=dev, dtype=_F32)
@@ -630,6 +640,23 @@ def workspace(device, nfloats=64 << 20):
     return _ws_cache[key]
 
 
+def conv_desc(device, **fields):
+    """A ConvDesc (include/coocc_hip.h coocc_conv_desc) holding ``fields`` and the split-K workspace of ``device``'s stream;
+    every other field is zero / NULL."""
+    ws = workspace(device)
+    return ConvDesc(ws=ptr(ws), ws_floats=ws.numel(), **fields)
+
+
+def launch_conv(d, device, name, flops):
+    """coocc_conv_fwd of descriptor ``d`` on ``device``, timed as kernel ``name``: a string, or a function that returns one and
+    is only called when the timer is on (the eager paths are host-bound)."""
+    if not TIMER.enabled:
+        _lib.conv_fwd(d, device)
+        return
+    with TIMER.region(name() if callable(name) else name, flops):
+        _lib.conv_fwd(d, device)
+
+
 def out_dim(n, k, s, p):
     return (n + 2 * p - k) // s + 1
 
@@ -638,8 +665,7 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
     """out = epi(conv(x)) on Rows.  res: Rows added before ReLU (res_mode 1).  ``twin_for``: the layers (PackedConv) that
     read the result next -- when one of them takes the split-f16 direct path the epilogue writes the H2 twin it needs
     (``out.h2``) next to the fp32 rows, which replaces that layer's conversion pass."""
-    Xo, Yo, Zo = (out_dim(x.X, pc.ksize, pc.stride, pc.pad), out_dim(x.Y, pc.ksize, pc.stride, pc.pad),
-                  out_dim(x.Z, pc.ksize, pc.stride, pc.pad))
+    Xo, Yo, Zo = (out_dim(n, pc.ksize, pc.stride, pc.pad) for n in (x.X, x.Y, x.Z))
     M = x.B * Xo * Yo * Zo
     if out is None:
         out = Rows(torch.empty(M, pc.Cout, device=x.t.device, dtype=_F32), x.B, Xo, Yo, Zo, pc.Cout)
@@ -647,41 +673,21 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
         out.h2 = out.h16 = None        # a caller-provided buffer is overwritten: whatever twins it carried are stale
     assert x.C == pc.Cin, "channel mismatch: %d vs %d" % (x.C, pc.Cin)
     rm = res_mode or (1 if res is not None else 0)
-    bf16 = CONV_DTYPE == "bf16"
-    f16 = CONV_DTYPE == "f16"
-    plan = None if (bf16 or f16) else wino_plan(x, pc, M, rm)
-    twin = bool(twin_for) and CONV_ENGINE == "h2" and not (bf16 or f16) and pc.Cout % 32 == 0 and takes_h2(out, twin_for)
-    if plan is not None:
+    family, plan, trim, taps = _route(x.B, x.X, x.Y, x.Z, pc, rm, splitk)
+    twin = wants_h2_twin(out, twin_for)
+    if family == "wino":
         return conv_rows_wino(x, pc, out, relu, res, plan, twin=twin)
-    ws = workspace(x.t.device)
-    d = ConvDesc()
-    d.in_, d.w, d.out = x.data(), ptr(pc.w), out.data()
-    d.scale, d.bias = ptr(pc.scale), ptr(pc.bias)
-    d.res = res.data() if res is not None else None
-    d.gather = None
-    d.out_rows = None
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = M, pc.Cin, pc.Cout, pc.taps
-    d.in_stride, d.out_stride = x.stride, out.stride
-    d.res_stride = res.stride if res is not None else 0
-    d.B, d.Xi, d.Yi, d.Zi, d.Xo, d.Yo, d.Zo = x.B, x.X, x.Y, x.Z, Xo, Yo, Zo
-    d.ksize, d.stride, d.pad = pc.ksize, pc.stride, pc.pad
-    d.relu, d.res_mode, d.splitk = int(relu), (res_mode or (1 if res is not None else 0)), splitk
-    d.tile_hint = TILE_HINT
-    d.mfma_dtype = 1 if bf16 else 0
-    taps = pc.taps
-    trim = None
-    if ZTRIM and pc._w_cube is not None:
-        # z taps that are in range for at least one output z; on thin grids (Z = 1, 2) the rest only multiply padding
-        ok = [kz for kz in range(3) if any(0 <= zo * pc.stride - pc.pad + kz < x.Z for zo in range(Zo))]
-        lo, hi = ok[0], ok[-1]
-        if hi - lo + 1 < 3:
-            trim = (lo, hi)
-            d.w = ptr(pc.ztrim_pack(lo, hi))
-            d.kx, d.ky, d.kz, d.px, d.py, d.pz = 3, 3, hi - lo + 1, pc.pad, pc.pad, pc.pad - lo
-            d.taps = taps = 9 * (hi - lo + 1)
+    dev = x.t.device
+    d = conv_desc(dev, out=out.data(), scale=ptr(pc.scale), bias=ptr(pc.bias), res=res.data() if res is not None else None,
+                  M=M, Cin=pc.Cin, Cout=pc.Cout, taps=taps, out_stride=out.stride, res_stride=res.stride if res is not None else 0,
+                  B=x.B, Xi=x.X, Yi=x.Y, Zi=x.Z, Xo=Xo, Yo=Yo, Zo=Zo, ksize=pc.ksize, stride=pc.stride, pad=pc.pad,
+                  relu=int(relu), res_mode=rm, splitk=splitk, tile_hint=TILE_HINT)
+    if trim is not None:
+        # z taps lo..hi only: the others read nothing but padding on this grid
+        d.kx, d.ky, d.kz, d.px, d.py, d.pz = 3, 3, trim[1] - trim[0] + 1, pc.pad, pc.pad, pc.pad - trim[0]
     same = pc.stride == 1 and (Xo, Yo, Zo) == (x.X, x.Y, x.Z)
-    if f16 and pc.Cin % 64 == 0 and pc._w_taps is not None and rm in (0, 1) and splitk in (0, 1) and out.coff == 0 and out.stride == pc.Cout:
+    flops = 2.0 * M * pc.Cin * pc.Cout * taps
+    if family == "f16" and out.coff == 0 and out.stride == pc.Cout:
         # configs[4]'s reduced-precision path: ONE v_mfma_f32_32x32x16_f16 per step on f16 operands that live in HBM as f16 rows
         # (2 bytes per element) -- written by the PRODUCER's epilogue (out16; Rows.h16) or, for inputs that came from a non-conv
         # kernel, by one conversion pass -- fp32 accumulate / BN / residual / ReLU; the fp32 rows are written as well (the
@@ -689,52 +695,47 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
         # constants cost bits f16 does not have).
         xh = x.h16
         if xh is None:
-            xh = torch.empty(x.B * x.V, pc.Cin, device=x.t.device, dtype=torch.float16)
+            xh = torch.empty(x.B * x.V, pc.Cin, device=dev, dtype=torch.float16)
             call("coocc_rows_to_f16", x.data(), x.stride, x.B * x.V, pc.Cin, ptr(xh))
-        out.h16 = torch.empty(M, pc.Cout, device=x.t.device, dtype=torch.float16) if pc.Cout % 4 == 0 else None
+        out.h16 = torch.empty(M, pc.Cout, device=dev, dtype=torch.float16) if pc.Cout % 4 == 0 else None
         d.in_, d.in_stride, d.w, d.mfma_dtype, d.alpha, d.splitk = ptr(xh), pc.Cin, ptr(pc.h1_pack(trim)), 4, 1.0, 1
         if out.h16 is not None:
             d.out16, d.out16_stride = ptr(out.h16), pc.Cout
-        with TIMER.region("k_gemm_h1z" if (same and taps > 1) else "k_gemm_h1w", 2.0 * M * pc.Cin * pc.Cout * taps):
-            _lib.conv_fwd(d, pc.w.device)
+        launch_conv(d, pc.w.device, "k_gemm_h1z" if (same and taps > 1) else "k_gemm_h1w", flops)
         return out
-    if (not bf16 and not f16 and CONV_ENGINE == "h2" and H2_DIRECT and pc.Cin % 32 == 0 and pc._w_taps is not None
-            and rm in (0, 1) and 2.0 * M * pc.Cin * pc.Cout * taps >= H2_DIRECT_MIN_FLOPS):
+    if family == "h2":
         # fp32-accurate split-f16 GEMM (csrc/gemm_h2.hip) for the layers the Winograd path leaves out (small grids, strided,
         # 1x1x1): the input rows are split into H2 rows once per layer, stride-1 "same" layers share one LDS image per 3 z taps
         # (k_gemm_h2z), the rest fetch one image per (chunk, tap) (k_gemm_h2w); the epilogue (folded BN, residual, ReLU) is the usual one
         if x.coff == 0 and x.C == pc.Cin:
             xh = h2_rows(x)                 # the producer's twin, or one conversion shared by every consumer of x
         else:
-            xh = scratch(x.t.device, "h2in", x.B * x.V * pc.Cin)
+            xh = scratch(dev, "h2in", x.B * x.V * pc.Cin)
             call("coocc_rows_to_h2", x.data(), x.stride, x.B * x.V, pc.Cin, 1.0, ptr(xh))
         d.in_, d.in_stride, d.w, d.mfma_dtype, d.alpha = ptr(xh), pc.Cin, ptr(pc.h2_pack(trim)), 3, 1.0
         if INKERNEL_REDUCE:
-            sem = tile_sem(x.t.device)      # split-K layers reduce in-kernel (last workgroup of a tile): no k_conv_reduce launch
+            sem = tile_sem(dev)      # split-K layers reduce in-kernel (last workgroup of a tile): no k_conv_reduce launch
             d.tile_sem, d.tile_sem_ints = ptr(sem), sem.numel()
         if twin and out.coff == 0 and out.stride % 4 == 0 and (res is None or res.stride % 4 == 0):
-            out.h2 = torch.empty(M, pc.Cout, device=x.t.device, dtype=_F32)
+            out.h2 = torch.empty(M, pc.Cout, device=dev, dtype=_F32)
             d.out_h2_twin = ptr(out.h2)
-        with TIMER.region("k_gemm_h2z direct" if (same and taps > 1) else "k_gemm_h2w", 2.0 * M * pc.Cin * pc.Cout * taps):
-            _lib.conv_fwd(d, pc.w.device)
+        launch_conv(d, pc.w.device, "k_gemm_h2z direct" if (same and taps > 1) else "k_gemm_h2w", flops)
         return out
+    # the fp32-MFMA kernels (bf16: operands rounded to bf16), and the f16 layers whose output is not whole rows
+    bf16 = CONV_DTYPE == "bf16"
     if bf16 and BF16_PRECONVERT and pc.Cin % 64 == 0 and pc._w_taps is not None and taps > 1:    # 1x1x1: HBM-bound either way
         # operands bf16 in memory (k_conv_bf16w): the activations are rounded once per layer into a scratch buffer, the
-        # weights once per pack
-        xb = _bf16_buffer(x.t.device, x.B * x.V * pc.Cin)
+        # weights once per pack; stride-1 "same" layers share the tile between z taps (k_conv_bf16z)
+        xb = _bf16_buffer(dev, x.B * x.V * pc.Cin)
         call("coocc_rows_to_bf16", x.data(), x.stride, x.B * x.V, pc.Cin, ptr(xb))
-        wb = pc.bf16_pack(trim)
-        d.in_, d.in_stride, d.w, d.mfma_dtype = ptr(xb), pc.Cin, ptr(wb), 2
-    if not TIMER.enabled:
-        _lib.conv_fwd(d, pc.w.device)
-        return out
-    if d.mfma_dtype == 2:      # mirror of the dispatch in coocc_conv_fwd: stride-1 "same" layers share the tile between z taps
-        kname = "k_conv_bf16z" if (pc.stride == 1 and (Xo, Yo, Zo) == (x.X, x.Y, x.Z) and ZSHARE) else "k_conv_bf16w"
+        d.in_, d.in_stride, d.w, d.mfma_dtype = ptr(xb), pc.Cin, ptr(pc.bf16_pack(trim)), 2
+        name = "k_conv_bf16z" if (same and ZSHARE) else "k_conv_bf16w"
     else:
-        kname = "k_conv_bf16" if bf16 else conv_kernel_name(M, pc.Cout, False, 0, taps * -(-pc.Cin // 32),
-                                                         pc.ksize == 1 and pc.stride == 1 and pc.pad == 0)
-    with TIMER.region(kname, 2.0 * M * pc.Cin * pc.Cout * taps):
-        _lib.conv_fwd(d, pc.w.device)
+        d.in_, d.in_stride, d.mfma_dtype = x.data(), x.stride, 1 if bf16 else 0
+        d.w = ptr(pc.ztrim_pack(*trim) if trim is not None else pc.w)
+        name = "k_conv_bf16" if bf16 else lambda: conv_kernel_name(M, pc.Cout, False, 0, taps * -(-pc.Cin // 32),
+                                                                   pc.ksize == 1 and pc.stride == 1 and pc.pad == 0)
+    launch_conv(d, pc.w.device, name, flops)
     return out
 
 
@@ -746,24 +747,10 @@ def linear_rows(x2d, pc, relu=False, out=None, out_coff=0, in_coff=0, in_C=None)
         out = torch.empty(n, pc.Cout, device=x2d.device, dtype=_F32)
     if n == 0:
         return out
-    ws = workspace(x2d.device)
-    d = ConvDesc()
-    d.in_ = ctypes.c_void_p(x2d.data_ptr() + 4 * in_coff)
-    d.w = ptr(pc.w)
-    d.out = ctypes.c_void_p(out.data_ptr() + 4 * out_coff)
-    d.scale, d.bias = ptr(pc.scale), ptr(pc.bias)
-    d.res = None
-    d.gather = None
-    d.out_rows = None
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = n, Cin, pc.Cout, 1
-    d.in_stride, d.out_stride, d.res_stride = x2d.shape[1], out.shape[1], 0
-    d.B, d.Xi, d.Yi, d.Zi, d.Xo, d.Yo, d.Zo = 1, n, 1, 1, n, 1, 1
-    d.ksize, d.stride, d.pad = 1, 1, 0
-    d.relu, d.res_mode, d.splitk = int(relu), 0, 0
-    d.tile_hint = TILE_HINT
-    with TIMER.region(conv_kernel_name(n, pc.Cout, False, 0, -(-Cin // 32), True), 2.0 * n * Cin * pc.Cout):
-        _lib.conv_fwd(d, x2d.device)
+    d = conv_desc(x2d.device, in_=ptr(x2d, offset=in_coff), w=ptr(pc.w), out=ptr(out, offset=out_coff), scale=ptr(pc.scale),
+                  bias=ptr(pc.bias), M=n, Cin=Cin, Cout=pc.Cout, taps=1, in_stride=x2d.shape[1], out_stride=out.shape[1],
+                  B=1, Xi=n, Yi=1, Zi=1, Xo=n, Yo=1, Zo=1, ksize=1, stride=1, relu=int(relu), tile_hint=TILE_HINT)
+    launch_conv(d, x2d.device, lambda: conv_kernel_name(n, pc.Cout, False, 0, -(-Cin // 32), True), 2.0 * n * Cin * pc.Cout)
     return out
 
 
@@ -773,21 +760,10 @@ def linear_rows_h2(xh, n, Cin, pc, relu=False, out=None, out_coff=0, out_h2=Fals
     dev = xh.device
     if out is None:
         out = torch.empty(n, pc.Cout, device=dev, dtype=_F32)
-    ws = workspace(dev)
-    d = ConvDesc()
-    d.in_, d.w = ptr(xh), ptr(pc.h2_pack())
-    d.out = ctypes.c_void_p(out.data_ptr() + 4 * out_coff)
-    d.scale, d.bias = ptr(pc.scale), ptr(pc.bias)
-    d.res = d.gather = d.out_rows = None
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = n, Cin, pc.Cout, 1
-    d.in_stride, d.out_stride, d.res_stride = Cin, out.shape[1], 0
-    d.B, d.Xi, d.Yi, d.Zi, d.Xo, d.Yo, d.Zo = 1, n, 1, 1, n, 1, 1
-    d.ksize, d.stride, d.pad = 1, 1, 0
-    d.relu, d.res_mode, d.splitk = int(relu), 0, 1
-    d.mfma_dtype, d.alpha, d.out_h2 = 3, 1.0, int(out_h2)
-    with TIMER.region("k_gemm_h2w linear", 2.0 * n * Cin * pc.Cout):
-        _lib.conv_fwd(d, dev)
+    d = conv_desc(dev, in_=ptr(xh), w=ptr(pc.h2_pack()), out=ptr(out, offset=out_coff), scale=ptr(pc.scale), bias=ptr(pc.bias),
+                  M=n, Cin=Cin, Cout=pc.Cout, taps=1, in_stride=Cin, out_stride=out.shape[1], B=1, Xi=n, Yi=1, Zi=1, Xo=n, Yo=1,
+                  Zo=1, ksize=1, stride=1, relu=int(relu), splitk=1, mfma_dtype=3, alpha=1.0, out_h2=int(out_h2))
+    launch_conv(d, dev, "k_gemm_h2w linear", 2.0 * n * Cin * pc.Cout)
     return out
 
 
@@ -796,9 +772,7 @@ def rows_to_h2(x2d, C=None, coff=0, name="h2rows"):
     n = x2d.shape[0]
     C = C if C is not None else x2d.shape[1]
     xh = scratch(x2d.device, name, n * C)
-    src = _lib.DevPtr(x2d.data_ptr() + 4 * coff)
-    src._keep = x2d
-    call("coocc_rows_to_h2", src, x2d.shape[1], n, C, 1.0, ptr(xh))
+    call("coocc_rows_to_h2", ptr(x2d, offset=coff), x2d.shape[1], n, C, 1.0, ptr(xh))
     return xh
 
 
@@ -826,39 +800,25 @@ def gather_conv_rows(src, src_coff, pc, gather, out_rows, dst, dst_coff, gate_co
     K, M = gather.shape
     if M == 0:
         return
-    ws = workspace(src.device)
-    d = ConvDesc()
-    d.in_ = ctypes.c_void_p(src.data_ptr() + 4 * src_coff)
-    d.w = ptr(pc.w)
-    d.out = ctypes.c_void_p(dst.data_ptr() + 4 * dst_coff)
-    d.scale, d.bias = None, ptr(pc.bias)
-    d.res = ctypes.c_void_p(dst.data_ptr() + 4 * gate_coff)
-    d.gather = ptr(gather, torch.int32)
-    d.out_rows = ptr(out_rows, torch.int32)
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = M, C, pc.Cout, K
-    d.in_stride, d.out_stride, d.res_stride = src.shape[1], dst.shape[1], dst.shape[1]
-    d.B, d.Xi, d.Yi, d.Zi, d.Xo, d.Yo, d.Zo = 1, src.shape[0], 1, 1, 1, 1, 1     # Xi = number of source rows
-    d.ksize, d.stride, d.pad = 1, 1, 0
-    d.relu, d.res_mode, d.splitk = int(relu), 2, 1
-    d.tile_hint = TILE_HINT
+    d = conv_desc(src.device, in_=ptr(src, offset=src_coff), w=ptr(pc.w), out=ptr(dst, offset=dst_coff), bias=ptr(pc.bias),
+                  res=ptr(dst, offset=gate_coff), gather=ptr(gather, torch.int32), out_rows=ptr(out_rows, torch.int32),
+                  M=M, Cin=C, Cout=pc.Cout, taps=K, in_stride=src.shape[1], out_stride=dst.shape[1], res_stride=dst.shape[1],
+                  B=1, Xi=src.shape[0], Yi=1, Zi=1, Xo=1, Yo=1, Zo=1,     # Xi = number of source rows
+                  ksize=1, stride=1, relu=int(relu), res_mode=2, splitk=1, tile_hint=TILE_HINT)
     if count_dev is not None:
         d.M_dev, d.gather_stride = ptr(count_dev, torch.int32), M
-    kname = conv_kernel_name(M, pc.Cout, True)
-    if g1_h2_capable(pc, C):
+    h2 = g1_h2_capable(pc, C)
+    if h2:
         # split-f16 engine: the source slot is converted once ([rows, C] H2 rows: 13 us for 80 k rows), the row-table kernel
         # gathers 128-byte chunks of it (k_gemm_h2w<TABLE>); 118 -> ~40 us per call at configs[1]
         if src_h2 is not None and src_h2[1] <= src_coff and src_coff + C <= src_h2[1] + src_h2[2] and (src_coff - src_h2[1]) % 32 == 0:
             sh, c0, n = src_h2
-            hp = _lib.DevPtr(sh.data_ptr() + 4 * (src_coff - c0))
-            hp._keep = sh
-            d.in_, d.in_stride = hp, n
+            d.in_, d.in_stride = ptr(sh, offset=src_coff - c0), n
         else:
             sh = rows_to_h2(src, C, src_coff, name="g1rows")
             d.in_, d.in_stride = ptr(sh), C
-        d.w, d.mfma_dtype, d.alpha, kname = ptr(pc.h2_pack()), 3, 1.0, "k_gemm_h2w"
-    with TIMER.region(kname, 2.0 * M * C * pc.Cout * K):
-        _lib.conv_fwd(d, src.device)
+        d.w, d.mfma_dtype, d.alpha = ptr(pc.h2_pack()), 3, 1.0
+    launch_conv(d, src.device, "k_gemm_h2w" if h2 else lambda: conv_kernel_name(M, pc.Cout, True), 2.0 * M * C * pc.Cout * K)
 
 
 class PackCache:

@@ -613,24 +613,15 @@ class BiFuser_N(nn.Module):
         Co = pd.Cout
         # P[u][t][n] = W_t[n, :] . cat4[u, C:3C] for the occupied rows u
         P = core.scratch(dev, "c0P", Np * 27 * Co)
-        d = _lib.ConvDesc()
-        ws = core.workspace(dev)
-        src = _lib.DevPtr(cat4.t.data_ptr() + 4 * (cat4.coff + C))
-        src._keep = cat4.t
-        d.in_, d.w, d.out = src, ptr(ps.w), ptr(P)
-        d.scale = d.bias = d.res = d.out_rows = None
-        d.gather = ptr(lin_pts)
-        d.ws, d.ws_floats = ptr(ws), ws.numel()
-        d.M, d.Cin, d.Cout, d.taps = Np, 2 * C, 27 * Co, 1
-        d.in_stride, d.out_stride, d.res_stride = cat4.stride, 27 * Co, 0
-        d.B = d.Yi = d.Zi = d.Xo = d.Yo = d.Zo = 1
-        d.Xi = V                      # number of input rows (lets coocc_conv_fwd pick the pipelined row-table kernel)
-        d.ksize, d.stride, d.pad = 1, 1, 0
-        d.relu, d.res_mode, d.splitk, d.tile_hint = 0, 0, 1, core.TILE_HINT
+        src = ptr(cat4.t, offset=cat4.coff + C)
+        d = core.conv_desc(dev, in_=src, w=ptr(ps.w), out=ptr(P), gather=ptr(lin_pts), M=Np, Cin=2 * C, Cout=27 * Co, taps=1,
+                           in_stride=cat4.stride, out_stride=27 * Co, B=1, Yi=1, Zi=1, Xo=1, Yo=1, Zo=1,
+                           Xi=V,       # number of input rows (lets coocc_conv_fwd pick the pipelined row-table kernel)
+                           ksize=1, stride=1, splitk=1, tile_hint=core.TILE_HINT)
         if count_dev is not None:
             d.M_dev, d.gather_stride = ptr(count_dev, _I32), lin_pts.numel()
-        kname = core.conv_kernel_name(Np, 27 * Co, True)
-        if core.CONV_ENGINE == "h2" and core.H2_DIRECT and (2 * C) % 32 == 0:
+        h2 = core.CONV_ENGINE == "h2" and core.H2_DIRECT and (2 * C) % 32 == 0
+        if h2:
             # split-f16 engine: the occupied rows are gathered into a compact H2 operand [Np, 2C] (count on the device in
             # the static form), then a plain GEMM against the [27 Cout, 2C] matrix
             rh = core.scratch(dev, "c0rows", Np * 2 * C)
@@ -638,9 +629,9 @@ class BiFuser_N(nn.Module):
                  2 * C, 1.0, ptr(rh))
             d.in_, d.in_stride, d.w, d.gather, d.gather_stride = ptr(rh), 2 * C, ptr(ps.h2_pack()), None, 0
             d.Xi, d.Xo = Np, Np
-            d.mfma_dtype, d.alpha, kname = 3, 1.0, "k_gemm_h2w"
-        with core.TIMER.region(kname + " c0-sparse", 2.0 * Np * 2 * C * 27 * Co):
-            _lib.conv_fwd(d, dev)
+            d.mfma_dtype, d.alpha = 3, 1.0
+        core.launch_conv(d, dev, "k_gemm_h2w c0-sparse" if h2 else lambda: core.conv_kernel_name(Np, 27 * Co, True) + " c0-sparse",
+                         2.0 * Np * 2 * C * 27 * Co)
         vmap = torch.empty(V, device=dev, dtype=_I32)
         if count_dev is not None:
             call("coocc_voxel_index_map_dev", ptr(lin_pts), int(lin_pts.numel()), ptr(count_dev, _I32), V, ptr(vmap))

@@ -182,7 +182,7 @@ class OccHead(nn.Module):
         merged = (MERGED_PRED_Q and "pred_q" in p and core.CONV_DTYPE == "f32" and self.cascade_ratio == 2 and self._fine2_h2_ok()
                   and not self.training)
         first = p["pred_q"] if merged else p["pred"][0]
-        if core.CONV_ENGINE == "h2" and core.CONV_DTYPE == "f32" and o0.C % 32 == 0 and core.takes_h2(out, (first,)):
+        if core.wants_h2_twin(out, (first,)):
             tw = out.h2 = torch.empty_like(o0.t)
         call("coocc_occhead_mix_ex", levels, dims, L, ptr(wlogit), ptr(out.t), o0.B, o0.C, ptr(tw))
         if merged:

@@ -14,7 +14,7 @@ from torch import nn
 import os
 
 from . import _lib, core
-from ._lib import ConvDesc, call, host_f32, ptr
+from ._lib import call, host_f32, ptr
 from .backbone import build_bn
 from .core import PackCache, PackedConv, Rows, TILE_HINT, fold_bn, workspace
 from .registry import Registry
@@ -139,21 +139,12 @@ def sparse_conv(feats, Cin, pc, table, relu=True, res=None, out=None, out_rows=N
     out_h2 = torch.empty(Mo, pc.Cout, device=dev, dtype=_F32) if (twin and h2 and pc.Cout % 32 == 0) else None
     if Mo == 0:
         return (out, out_h2) if twin else out
-    ws = workspace(dev)
-    d = ConvDesc()
-    d.in_, d.w, d.out = ptr(feats), ptr(pc.w), ptr(out)
-    d.scale, d.bias = ptr(pc.scale), ptr(pc.bias)
-    d.res = ptr(res)
-    d.gather = ptr(table, _I32)
-    d.out_rows = ptr(out_rows, _I32) if out_rows is not None else None
-    d.ws, d.ws_floats = ptr(ws), ws.numel()
-    d.M, d.Cin, d.Cout, d.taps = Mo, Cin, pc.Cout, taps
-    d.in_stride, d.out_stride = feats.shape[1], out.shape[1]
-    d.res_stride = res.shape[1] if res is not None else 0
-    d.B = d.Yi = d.Zi = d.Xo = d.Yo = d.Zo = 1
-    d.Xi = feats.shape[0]          # number of input rows (lets coocc_conv_fwd pick the pipelined row-table kernel)
-    d.ksize, d.stride, d.pad = 1, 1, 0
-    d.relu, d.res_mode, d.splitk, d.tile_hint = int(relu), (1 if res is not None else 0), 1, TILE_HINT
+    d = core.conv_desc(dev, in_=ptr(feats), w=ptr(pc.w), out=ptr(out), scale=ptr(pc.scale), bias=ptr(pc.bias), res=ptr(res),
+                       gather=ptr(table, _I32), out_rows=ptr(out_rows, _I32), M=Mo, Cin=Cin, Cout=pc.Cout, taps=taps,
+                       in_stride=feats.shape[1], out_stride=out.shape[1], res_stride=res.shape[1] if res is not None else 0,
+                       B=1, Yi=1, Zi=1, Xo=1, Yo=1, Zo=1,
+                       Xi=feats.shape[0],       # number of input rows (lets coocc_conv_fwd pick the pipelined row-table kernel)
+                       ksize=1, stride=1, relu=int(relu), res_mode=1 if res is not None else 0, splitk=1, tile_hint=TILE_HINT)
     kname = "k_conv"
     if h2:
         if feats_h2 is None:
@@ -163,8 +154,7 @@ def sparse_conv(feats, Cin, pc, table, relu=True, res=None, out=None, out_rows=N
         d.mfma_dtype, d.alpha, kname = 3, 1.0, "k_gemm_h2w"
         if out_h2 is not None:
             d.out_h2_twin = ptr(out_h2)
-    with _lib.TIMER.region("%s<sparse table %d->%d>" % (kname, Cin, pc.Cout), 2.0 * Mo * Cin * pc.Cout * taps):
-        _lib.conv_fwd(d, pc.w.device)
+    core.launch_conv(d, pc.w.device, "%s<sparse table %d->%d>" % (kname, Cin, pc.Cout), 2.0 * Mo * Cin * pc.Cout * taps)
     return (out, out_h2) if twin else out
 
 

@@ -73,7 +73,7 @@ class FPN3D(nn.Module):
             c, f = lat[i], lat[i - 1]
             f.h16 = f.h2 = None   # the rows change in place: the 16-bit copies the lateral conv's epilogue wrote are stale
             tw = None
-            if core.CONV_ENGINE == "h2" and core.CONV_DTYPE == "f32" and f.C % 32 == 0 and core.takes_h2(f, (p["out"][i - 1],)):
+            if core.wants_h2_twin(f, (p["out"][i - 1],)):
                 tw = f.h2 = torch.empty(f.B * f.V, f.C, device=f.t.device, dtype=torch.float32)
             call("coocc_upsample_add_trilinear_ex", ptr(c.t), ptr(f.t), f.B, f.C, c.X, c.Y, c.Z, f.X, f.Y, f.Z, ptr(tw))
         obr = core.Fork(3, dev, enable=self.num_out > 1)
