@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from co_occ_amd import _lib, core
 from co_occ_amd._lib import call, ptr
 from test_gpu_conv import bn_like, rows_of
-from util import assert_close
+from util import assert_close, kernels_start, kernels_stop, train_judge
 
 pytestmark = pytest.mark.gpu
 
@@ -236,14 +236,18 @@ def test_training_layers_on_the_split_f16_engine_match_torch_at_any_gradient_sca
         xd = r2d(x).to(dev).requires_grad_(True)
         wd = w.to(dev).requires_grad_(True)
         monkeypatch.setattr(ag, "TRAIN_WINO", wino)
+        kernels_start()
         yd, _ = ag.conv3d_rows(xd, wd, (B, X, Y, Z), stride=stride, pad=k // 2, relu=True)
         yd.backward(r2d(up).to(dev))
+        names = kernels_stop()
         torch.cuda.synchronize()
         core.check_h2_overflow()
         what = "k%d s%d wino=%d Z=%d |dy|~%g" % (k, stride, wino, Z, gmag)
         assert_close(yd.detach().cpu(), r2d(yr.detach()), what="h2 train fwd " + what)
         assert_close(xd.grad.cpu(), r2d(xr.grad), what="h2 train dgrad " + what)
         assert_close(wd.grad.cpu(), wr.grad, what="h2 train wgrad " + what)
+        # the own-scale float64 judge (tests/util.py assert_precise): at |dy| ~ 1e-6 the assertions above pass a kernel returning zeros
+        train_judge(x, w, up, yd, xd.grad, wd.grad, k, stride, wino, what, names)
 
 
 @pytest.mark.parametrize("tile,dgrad", [(4, 0), (4, 1), (2, 0)])
