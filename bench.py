@@ -24,9 +24,12 @@ Outputs are checked bit for bit against sequential eager calls in tests/test_gpu
 the weight-gradient GEMMs); ``--with-lidar``: frames carry a raw point cloud and the LiDAR producer (voxelisation -> VFE -> sparse
 encoder) runs inside the step on the prefetch stream.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the Winograd-domain split-f16 GEMM k_gemm_h2z, priced against
-the dense f16 MFMA peak; per-kernel HIP events from an eager pass right after the timed region, *_alone = nothing else on the
-GPU), `roofline_pool`, `roofline_render[_r101]` and, at N=1, `cpu_baseline` (the oracle's CPU restatement timed on this host).
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing more: set-up, --warmup steps, the --steps
+timed steps, --dump-outputs, the line.  ``--full`` adds what takes runs of its own after the timed region: `roofline` (dominant
+kernel: the Winograd-domain split-f16 GEMM k_gemm_h2z, priced against the dense f16 MFMA peak; per-kernel HIP events from an
+eager pass right after the timed region, *_alone = nothing else on the GPU), `roofline_pool`, `roofline_render[_r101]`,
+`roofline_isolated`, at N=1 `cpu_baseline` (the oracle's CPU restatement timed on this host) and `also` (a second workload).
+Eager runs (--graph 0, --train) take their per-kernel events inside the timed region, so their `roofline` is in every line.
 """
 import argparse
 import json
@@ -814,12 +817,17 @@ def main():
     ap.add_argument("--also", default="auto",
                     help="a second, SHORT measurement appended to the JSON line as \"also\": {name: {value, ms_per_step, ...}} -- north_star's literal "
                          "stress workload (--config stress200_r101: 200x200x16 fused grid + 6 x 896 x 1600 frames), 20 steps in 2 windows in a "
-                         "child process after the main measurement (<= 25 s).  auto: only for the default command's workload (config r50, "
-                         "serving API, one GPU, no --train / --with-lidar / --shard rays); none: never; or a config name")
+                         "child process after the main measurement (<= 25 s).  auto: only with --full and for the default command's workload "
+                         "(config r50, serving API, one GPU, no --train / --with-lidar / --shard rays); none: never; or a config name")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, after the timed region: the per-kernel eager passes behind "
+                         "`roofline` / `roofline_*` (graph-replayed runs) and `roofline_isolated` (--graph 0 with 2 streams), the r101 "
+                         "render roofline, the CPU baseline and --also auto")
     ap.add_argument("--diag", action="store_true", help="host-side issue times per sample to stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel event timing table to stderr")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="no per-kernel HIP events, inside the timed region or after it")
+    ap.add_argument("--kernel-table", action="store_true",
+                    help="print the per-kernel event timing table to stderr (graph-replayed runs: that of the --full eager pass)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, "
                          "at most 64 MB in all; an array that does not fit is written as a fixed seeded sample of its elements, "
@@ -1066,7 +1074,7 @@ def main():
             graph_info = dict(api="COOCC_Ray.simple_test(precomputed=...) -- the reference's per-sample call, synchronous", slots=1,
                               captured_graph=st_api["graph"], eager_reason=st_api["eager_reason"],
                               eager_fallbacks=(model._pipe1[1].fallbacks if model._pipe1 is not None else None))
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             # per-kernel durations cannot be taken inside a graph launch: an eager pass of the same step (one sample in flight,
             # search prefetched) with HIP events around every launch, right after the timed region
             n_e = max(8, min(20, args.steps))
@@ -1096,7 +1104,7 @@ def main():
                 roof.update(achieved_alone=r_al["achieved"], frac_alone=r_al["frac"], avg_launch_ms_alone=r_al["avg_launch_ms"],
                             note="achieved / frac: launches that share the CUs with the prefetched search of the next sample (as in the "
                                  "timed pipeline); *_alone: the same launches with nothing else on the GPU (6 samples, no prefetch)")
-    if S > 1 and not graphish and not args.no_kernel_timing:
+    if args.full and S > 1 and not graphish and not args.no_kernel_timing:
         # Kernel durations inside the S-stream pipeline include the contention between the samples in flight (that is the
         # point of it: one sample's low-occupancy tail runs under the other's GEMMs).  A short pass of the same pipeline with ONE
         # sample in flight (the next sample's pooling + search still prefetched) gives each kernel's own rate next to it.
@@ -1119,7 +1127,7 @@ def main():
         extra["roofline_isolated"] = dict(r_iso or {}, note="separate pass after the timed region: the same pipeline with one sample in flight (--streams 1)",
                                           all_convs=e_iso.get("roofline_all_convs"), render=e_iso.get("roofline_render"),
                                           pool=e_iso.get("roofline_pool"))
-    if rank == 0 and args.config == "r50" and not args.no_kernel_timing:
+    if args.full and rank == 0 and args.config == "r50" and not args.no_kernel_timing:
         extra["roofline_render_r101"] = render_r101_roofline(model, dev)
     jobs = 1 if SHARD[0] else world          # --shard rays: all ranks work on the same scene
     line = dict(metric="samples/sec (6-cam frame + sweep -> occ+render), 200x200x16 grid", value=round(jobs * args.steps / dt, 4),
@@ -1169,11 +1177,11 @@ def main():
     if probe is not None:
         line["stream_probe"] = dict(probe, note="untimed bursts before the warm-up: samples in flight chosen by the faster total "
                                                 "(--streams 1 / 2 fixes it)")
-    if world == 1 and not args.no_cpu_baseline and args.config != "openocc":   # cascade 4: ~10 M fine points, hours on the CPU
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config != "openocc":   # cascade 4: ~10 M fine points, hours on the CPU
         line["cpu_baseline"] = cpu_baseline(sd, samples[0], args.config, WITH_POOL[0])
     also_cfg = None
     if args.also == "auto":
-        if (world == 1 and args.config == "r50" and args.api == "serving" and args.graph and not args.with_lidar and not SHARD[0]
+        if (args.full and world == 1 and args.config == "r50" and args.api == "serving" and args.graph and not args.with_lidar and not SHARD[0]
                 and args.dtype == "f32" and not args.no_cpu_baseline):
             also_cfg = "stress200_r101"
     elif args.also not in ("none", "0", ""):

@@ -1,6 +1,7 @@
-"""bench.py's contract, end to end on one GPU: the one-JSON-line output with ``roofline`` / ``cpu_baseline``-less fast settings,
-and the N > 1 path (one process per rank under torch.distributed.run, two dense streams per rank, ticketed collectives) with both
-ranks on cuda:0 over gloo -- the control flow the driver's scaling run takes, minus RCCL."""
+"""bench.py's contract, end to end on one GPU: the one-JSON-line output of a plain run and, with ``--full``, its ``roofline``
+objects (``cpu_baseline``-less fast settings), and the N > 1 path (one process per rank under torch.distributed.run, two dense
+streams per rank, ticketed collectives) with both ranks on cuda:0 over gloo -- the control flow the driver's scaling run takes,
+minus RCCL."""
 import json
 import os
 import socket
@@ -47,9 +48,9 @@ def _check_dump(d):
 
 
 def test_default_line_is_the_graph_pipeline_with_the_contract_fields(tmp_path):
-    """The driver's command: the dense stage of every sample is one hipGraph launch; the line says so and carries the roofline
-    objects (per-kernel HIP events from the eager pass after the timed region)."""
-    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--no-cpu-baseline", "--also", "r101",
+    """The driver's command with ``--full``: the dense stage of every sample is one hipGraph launch; the line says so and carries
+    the roofline objects (per-kernel HIP events from the eager pass after the timed region)."""
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--full", "--no-cpu-baseline", "--also", "r101",
               "--dump-outputs", str(tmp_path)])
     _check_contract(d, 12, 2)
     _check_dump(str(tmp_path))
@@ -65,9 +66,24 @@ def test_default_line_is_the_graph_pipeline_with_the_contract_fields(tmp_path):
     assert a["config"]["render_maps"] == "6x896x1600" and "also" not in a
 
 
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """The driver's command without ``--full``: set-up, warm-up, the timed steps, the dump and the line -- none of the passes after
+    the timed region (per-kernel eager passes, r101 render, CPU baseline, ``also``)."""
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "12", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "graph"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 12 and d["warmup"] == 2 and d["unit"] == "samples/s" and d["higher_is_better"]
+    assert d["dtype"] == "f32 (split-f16 products, fp32 accumulate)" and "hipGraph" in d["config"]["pipeline"]
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 0.05 * d["value"]
+    assert d["roofline"] is None and not any(k.startswith("roofline_") for k in d)
+    assert "cpu_baseline" not in d and "also" not in d
+    _check_dump(str(tmp_path))
+
+
 def test_eager_line_reports_its_stream_probe(tmp_path):
     """--graph 0: every launch issued from Python; the number of samples in flight is chosen from untimed bursts and reported."""
-    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--graph", "0",
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline", "--graph", "0",
               "--dump-outputs", str(tmp_path)])
     _check_contract(d, 8, 2)
     _check_dump(str(tmp_path))
@@ -98,7 +114,7 @@ def test_train_line_dumps_the_same_outputs_every_run(tmp_path):
 
 
 def test_two_streams_line_carries_the_alone_figures():
-    d = _run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--streams", "2", "--no-cpu-baseline", "--graph", "0"])
+    d = _run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--streams", "2", "--full", "--no-cpu-baseline", "--graph", "0"])
     _check_contract(d, 6, 2)
     assert d["config"]["samples_in_flight"] == 2 and "stream_probe" not in d
     assert 0 < d["roofline"]["frac_alone"] < 1 and "roofline_isolated" in d

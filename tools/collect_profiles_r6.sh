@@ -9,11 +9,11 @@ mkdir -p $O
 cd $R
 cd /tmp && export TMPDIR=/tmp
 timeout 300 python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2>&1      # clocks / caches warm before the recorded runs
-timeout 400 python $R/bench.py > $O/r6_bench_default.json 2> $O/r6_bench_default.err        # the driver's command
-timeout 300 python $R/bench.py --steps 40 --warmup 3 --no-cpu-baseline --kernel-table > $O/r6_bench_kernel_table.json 2> $O/r6_bench_kernel_table.txt
+timeout 400 python $R/bench.py --full > $O/r6_bench_default.json 2> $O/r6_bench_default.err        # the driver's command, every figure
+timeout 300 python $R/bench.py --steps 40 --warmup 3 --full --no-cpu-baseline --kernel-table > $O/r6_bench_kernel_table.json 2> $O/r6_bench_kernel_table.txt
 timeout 300 python $R/bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-kernel-timing --api simple_test > $O/r6_bench_api_simple_test.json 2>/dev/null
 timeout 300 python $R/bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-kernel-timing --api pipelined_test > $O/r6_bench_api_pipelined_test.json 2>/dev/null
-timeout 300 python $R/bench.py --steps 40 --warmup 3 --no-cpu-baseline --graph 0 > $O/r6_bench_eager.json 2>/dev/null
+timeout 300 python $R/bench.py --steps 40 --warmup 3 --full --no-cpu-baseline --graph 0 > $O/r6_bench_eager.json 2>/dev/null
 COOCC_CONV_ENGINE=f32 timeout 300 python $R/bench.py --steps 40 --warmup 3 --no-cpu-baseline > $O/r6_bench_engine_f32.json 2>/dev/null
 timeout 300 python $R/bench.py --train --steps 10 --warmup 2 > $O/r6_bench_train.json 2> $O/r6_bench_train.err
 COOCC_TRAIN_H2=0 timeout 300 python $R/bench.py --train --steps 10 --warmup 2 > $O/r6_bench_train_f32.json 2>/dev/null
@@ -21,7 +21,7 @@ timeout 300 python $R/bench.py --train --steps 10 --warmup 2 --train-prefetch 0 
 COOCC_TRAIN_H2_WGRAD=0 timeout 300 python $R/bench.py --train --steps 10 --warmup 2 > $O/r6_bench_train_wgrad_f32.json 2>/dev/null
 COOCC_TRAIN_H2_DGRAD=0 timeout 300 python $R/bench.py --train --steps 10 --warmup 2 > $O/r6_bench_train_dgrad_f32.json 2>/dev/null
 timeout 300 python $R/bench.py --train --steps 20 --warmup 3 --no-kernel-timing > $O/r6_bench_train_notimers.json 2>/dev/null
-timeout 400 python $R/bench.py --with-lidar --steps 40 --warmup 3 > $O/r6_bench_with_lidar.json 2>/dev/null
+timeout 400 python $R/bench.py --with-lidar --steps 40 --warmup 3 --full > $O/r6_bench_with_lidar.json 2>/dev/null
 rm -rf /tmp/tt
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tt -o s -- python $R/bench.py --train --steps 10 --warmup 2 > /tmp/tt_train.json 2>/dev/null
 python - > $O/r6_train_kernels.txt 2>&1 < /dev/null <<PY
@@ -36,10 +36,10 @@ PY
 ( echo "tools/kbench.py lidar (280 k points -> 120 k voxels -> SparseLiDAREnc8x), MI355X, round 6"; echo; echo "== COOCC_LIDAR_H2=1 (default: rule-book GEMMs with Cin % 32 == 0 on the split-f16 engine)"; COOCC_LIDAR_H2=1 timeout 300 python $R/tools/kbench.py lidar 2>&1 | grep -v amdgpu.ids; echo; echo "== COOCC_LIDAR_H2=0 (fp32-MFMA row-table kernels, rounds 1-3)"; COOCC_LIDAR_H2=0 timeout 300 python $R/tools/kbench.py lidar 2>&1 | grep -v amdgpu.ids ) > $O/r6_kbench_lidar.txt
 timeout 300 python $R/tools/serving_trace.py r50 36 6 3 0 2>&1 | grep -v amdgpu.ids > $O/r6_serving_trace.txt
 for cfg in r101 stress200 stress200_r101; do
-  timeout 400 python $R/bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline > $O/r6_bench_$cfg.json 2> $O/r6_bench_$cfg.err
+  timeout 400 python $R/bench.py --config $cfg --steps 20 --warmup 3 --full --no-cpu-baseline > $O/r6_bench_$cfg.json 2> $O/r6_bench_$cfg.err
 done
-timeout 400 python $R/bench.py --config openocc --steps 20 --warmup 3 --no-cpu-baseline > $O/r6_bench_openocc_f32.json 2>/dev/null
-timeout 400 python $R/bench.py --config openocc --dtype f16 --steps 20 --warmup 3 --no-cpu-baseline > $O/r6_bench_openocc_f16.json 2>/dev/null
+timeout 400 python $R/bench.py --config openocc --steps 20 --warmup 3 --full --no-cpu-baseline > $O/r6_bench_openocc_f32.json 2>/dev/null
+timeout 400 python $R/bench.py --config openocc --dtype f16 --steps 20 --warmup 3 --full --no-cpu-baseline > $O/r6_bench_openocc_f16.json 2>/dev/null
 # slots x dense streams x searches ahead
 for sp in "6 3 0" "6 2 0" "6 4 0" "8 3 0"; do
   set -- $sp

@@ -26,7 +26,7 @@ print(sys.argv[1].split("/")[-1], [r[0] for r in runs])
 PY
 }
 echo "loadavg $(cut -d' ' -f1-3 /proc/loadavg)"
-rec r2_bench_r101 --config r101 --steps 30 --no-cpu-baseline
-rec r2_bench_openocc_f32 --config openocc --steps 10 --warmup 2
-rec r2_bench_openocc_bf16 --config openocc --dtype bf16 --steps 10 --warmup 2
-rec r2_bench_stress200 --config stress200 --steps 6 --warmup 1 --no-cpu-baseline
+rec r2_bench_r101 --config r101 --steps 30 --full --no-cpu-baseline
+rec r2_bench_openocc_f32 --config openocc --steps 10 --warmup 2 --full
+rec r2_bench_openocc_bf16 --config openocc --dtype bf16 --steps 10 --warmup 2 --full
+rec r2_bench_stress200 --config stress200 --steps 6 --warmup 1 --full --no-cpu-baseline
