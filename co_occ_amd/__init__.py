@@ -16,6 +16,7 @@ from .neck import FPN3D
 from .head import OccHead
 from .view_transformer import ViewTransformerLiftSplatShootVoxel
 from .render import MLP, raw2outputs, render_block, sample_along_camera_ray, volume_sampling
+from .lidar_trunk import SECOND3D, SECOND3DFPN
 from .detector import COOCC_Ray, COOCC_Ray_L
 from .view_transformer import get_frustum
 from . import losses

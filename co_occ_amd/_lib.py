@@ -26,7 +26,7 @@ class ConvDesc(ctypes.Structure):
                                      "relu", "res_mode", "splitk", "tile_hint", "kx", "ky", "kz", "px", "py", "pz",
                                      "wgroup_rows", "mfma_dtype")] + [("alpha", ctypes.c_float), ("M_dev", c_void_p), ("gather_stride", c_int), ("out16", c_void_p), ("out16_stride", c_int), ("out_h2", c_int),
                                                                    ("out_h2_twin", c_void_p), ("tile_sem", c_void_p), ("tile_sem_ints", c_int),
-                                                                  ("alpha_dev", c_void_p)]
+                                                                  ("alpha_dev", c_void_p), ("sx", c_int), ("sy", c_int), ("sz", c_int)]
 
 
 class SearchDesc(ctypes.Structure):
@@ -173,6 +173,8 @@ SIGNATURES = {
     "coocc_bn_backward_dx": (I, [P, P, P, I, I, P, P, P, F, I, P, P, ctypes.c_double, P, P, P]),
     "coocc_predict_labels": (I, [P, L, L, L, L, I, I, I, I, I, I, I, P, P]),
     "coocc_eval_semantic": (I, [P, L, L, L, L, I, I, I, I, P, P, I, I, I, I, I, P, P]),
+    "coocc_fpn_sum": (I, [P, P, I, I, I, I, I, I, P, I, P, P]),
+    "coocc_zyx_to_rows": (I, [P, P, I, I, I, I, I, I, I, P]),
     "coocc_lidarseg_points": (I, [P, L, L, L, L, I, I, I, I, P, L, L, I, I, P, I, I, P, P, I, P, P]),
 }
 

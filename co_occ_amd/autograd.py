@@ -153,6 +153,7 @@ class _DevWinoF32:
         self.Cin, self.Cout = (Cout, Cin) if dgrad else (Cin, Cout)
         self.scale, self.bias = scale, bias
         self._w_raw, self.wino_tile = True, None
+        self.wino_kz, self.aniso = 3, False       # 3x3x3 stride-1 layers only (core.conv_rows_wino)
         self._w5, self._dgrad, self._packs = w5, int(bool(dgrad)), {}
         self.operand_scale_dev = None         # split-f16 engine, dgrad: {scale, 1 / scale} of the gradient rows, chosen on the device
 

@@ -235,12 +235,39 @@ def fold_bn(bn, conv_bias=None):
     return scale.float(), bias.float()
 
 
-class PackedConv:
-    """A conv/linear layer in the layout coocc_conv_fwd consumes (+ folded norm)."""
+def zyx_weight(w):
+    """A conv weight of the reference's [B,C,Z,Y,X] modules, [N,C,kD,kH,kW] = [N,C,kz,ky,kx], in this package's axis order
+    [N,C,kx,ky,kz] (tap t = (dx*ky + dy)*kz + dz after flattening)."""
+    return w.detach().permute(0, 1, 4, 3, 2).contiguous()
 
-    def __init__(self, weight, bn=None, bias=None, ksize=1, stride=1, pad=0, tap_major=False, taps=None):
+
+def deconv_weight(w, s):
+    """nn.ConvTranspose3d(kernel = stride = (1,s,s)) weight [Cin,Cout,1,s,s] ((kz,ky,kx) order) as the pointwise GEMM that produces
+    every coarse voxel's s*s children: [s*s*Cout, Cin], row (kx*s + ky)*Cout + co  (out[x*s + kx, y*s + ky] = W[:, co, 0, ky, kx] . in[x, y])."""
+    cin, cout = w.shape[:2]
+    assert tuple(w.shape[2:]) == (1, s, s), "deconv kernel %s is not (1,%d,%d)" % (tuple(w.shape[2:]), s, s)
+    return w.detach()[:, :, 0].permute(3, 2, 1, 0).reshape(s * s * cout, cin).contiguous()
+
+
+class PackedConv:
+    """A conv/linear layer in the layout coocc_conv_fwd consumes (+ folded norm).  Cubic by default (``ksize`` / ``stride`` /
+    ``pad``); ``kernel`` = (kx,ky,kz) with ``strides`` = (sx,sy,sz) and ``pads`` = (px,py,pz) describe an anisotropic layer
+    (weight [Cout,Cin,kx,ky,kz]: ``zyx_weight`` of a reference [.,.,kz,ky,kx] one), e.g. SECOND3D's 3x3x1 convs."""
+
+    def __init__(self, weight, bn=None, bias=None, ksize=1, stride=1, pad=0, tap_major=False, taps=None, kernel=None,
+                 strides=None, pads=None):
         w = weight.detach().float().cpu().contiguous()
         self.Cout = w.shape[0]
+        self.aniso = kernel is not None
+        if self.aniso:
+            assert not tap_major and taps is None and len(kernel) == 3
+            self.kernel = tuple(int(k) for k in kernel)
+            self.strides = tuple(int(v) for v in (strides or (1, 1, 1)))
+            self.pads = tuple(int(v) for v in (pads if pads is not None else [(k - 1) // 2 for k in self.kernel]))
+            taps = self.kernel[0] * self.kernel[1] * self.kernel[2]
+            ksize, stride, pad = self.desc_scalars()
+        else:
+            self.kernel, self.strides, self.pads = (ksize,) * 3, (stride,) * 3, (pad,) * 3
         if taps is None:
             taps = ksize ** 3
         if tap_major:
@@ -252,8 +279,12 @@ class PackedConv:
         self.taps, self.ksize, self.stride, self.pad = taps, ksize, stride, pad
         # raw weights kept on the host for the lazily built Winograd packs
         self._w_raw = w if (ksize == 3 and stride == 1 and pad == 1 and not tap_major and taps == 27) else None
+        self.wino_kz = 3             # z taps of the Winograd-domain GEMM: 3, or 1 for a 3x3x1 layer
+        if self.aniso and self.kernel[:2] == (3, 3) and self.kernel[2] in (1, 3) and self.strides == (1, 1, 1) and \
+                self.pads == (1, 1, self.kernel[2] // 2):
+            self._w_raw, self.wino_kz = w, self.kernel[2]
         # cubic 3x3x3 weights also kept for the z-trimmed packs (conv_rows: taps that only ever see z padding)
-        self._w_cube = w.view(self.Cout, self.Cin, 3, 3, 3) if (ksize == 3 and not tap_major and taps == 27) else None
+        self._w_cube = w.view(self.Cout, self.Cin, 3, 3, 3) if (ksize == 3 and not tap_major and taps == 27 and not self.aniso) else None
         self._ztrim = {}
         self._wino = {}
         self._bf16 = {}
@@ -274,6 +305,22 @@ class PackedConv:
             self.scale = None
             self.bias = bias.detach().float().to(dev).contiguous() if bias is not None else None
 
+
+    def desc_scalars(self):
+        """(ksize, stride, pad) of the descriptor's scalar fields.  A cubic layer: its own values.  An anisotropic one: the
+        largest extent / stride / padding -- the library reads kx.., px.., sx.. for the geometry and uses the scalar ``stride`` only
+        to ask "is every axis stride 1", which max() answers.  Host code asks ``kernel`` / ``strides`` / ``pads``
+        (``is_pointwise``, ``is_unit_stride``), never these."""
+        return max(self.kernel), max(self.strides), max(self.pads)
+
+    @property
+    def is_unit_stride(self):
+        return self.strides == (1, 1, 1)
+
+    @property
+    def is_pointwise(self):
+        """1x1x1, stride 1, no padding: input row = output row."""
+        return self.kernel == (1, 1, 1) and self.strides == (1, 1, 1) and self.pads == (0, 0, 0)
 
     def ztrim_pack(self, lo, hi):
         """Pack of the z taps lo..hi only (3 x 3 x (hi-lo+1) kernel): the other z taps read nothing but padding
@@ -356,15 +403,16 @@ class PackedConv:
         return self._bf16[key]
 
     def wino_h2_pack(self, tile):
-        """(tile+2)^2 H2 packs of U[p][dz] = (G g G^T)[xi][eta][dz] (taps = 3), split from the fp64 products."""
+        """(tile+2)^2 H2 packs of U[p][dz] = (G g G^T)[xi][eta][dz] (taps = 3, or 1 for a 3x3x1 layer), split from the fp64 products."""
         key = ("h2", tile)
         if key not in self._wino:
             G = self._wino_G(tile)
             n2 = G.shape[0] ** 2
-            w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, 3)
-            U = torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(n2, self.Cout, self.Cin, 3)
+            kz = self.wino_kz
+            w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, kz)
+            U = torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(n2, self.Cout, self.Cin, kz)
             npad = -(-self.Cout // 128) * 128
-            Up = torch.zeros(n2, npad, self.Cin, 3, dtype=torch.float64)
+            Up = torch.zeros(n2, npad, self.Cin, kz, dtype=torch.float64)
             Up[:, :self.Cout] = U
             self._wino[key] = torch.stack([self._h2_layout(Up[p]) for p in range(n2)], 0).to(self.w.device)
         return self._wino[key]
@@ -394,13 +442,14 @@ class PackedConv:
                 G = torch.tensor([[1, 0, 0], [1 / 3, 1 / 3, 1 / 3], [-1 / 3, 1 / 3, -1 / 3], [-16 / 15, -8 / 15, -4 / 15],
                                   [1 / 15, -2 / 15, 4 / 15], [0, 0, 1]], dtype=torch.float64)
             n2 = G.shape[0] ** 2
-            w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, 3)                 # [n, c, kx, ky, kz]
-            U = torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(n2, self.Cout, self.Cin, 3).float().contiguous()
+            kz = self.wino_kz
+            w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, kz)                # [n, c, kx, ky, kz]
+            U = torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(n2, self.Cout, self.Cin, kz).float().contiguous()
             lib = _lib.load()
-            n = lib.coocc_conv_pack_weights(ctypes.c_void_p(U[0].data_ptr()), self.Cout, self.Cin, 3, 0, None)
+            n = lib.coocc_conv_pack_weights(ctypes.c_void_p(U[0].data_ptr()), self.Cout, self.Cin, kz, 0, None)
             packed = torch.empty(n2, n, dtype=_F32)
             for p in range(n2):
-                lib.coocc_conv_pack_weights(ctypes.c_void_p(U[p].data_ptr()), self.Cout, self.Cin, 3, 0,
+                lib.coocc_conv_pack_weights(ctypes.c_void_p(U[p].data_ptr()), self.Cout, self.Cin, kz, 0,
                                             ctypes.c_void_p(packed[p].data_ptr()))
             self._wino[tile] = packed.to(self.w.device)
         return self._wino[tile]
@@ -547,12 +596,12 @@ def ztrim_range(Zin, Zout, stride, pad):
 
 def _route(B, X, Y, Z, pc, rm, splitk):
     """``route`` -> (family, Winograd plan or None, z trim (lo, hi) or None, taps after the trim)."""
-    Zo = out_dim(Z, pc.ksize, pc.stride, pc.pad)
-    M = B * out_dim(X, pc.ksize, pc.stride, pc.pad) * out_dim(Y, pc.ksize, pc.stride, pc.pad) * Zo
+    Xo, Yo, Zo = out_dims(X, Y, Z, pc)
+    M = B * Xo * Yo * Zo
     bf16, f16 = CONV_DTYPE == "bf16", CONV_DTYPE == "f16"
     plan = None if (bf16 or f16) else _wino_plan_geom(B, X, Y, Z, pc, M, rm)
     if plan is not None:
-        return "wino", plan, None, 3
+        return "wino", plan, None, pc.wino_kz
     taps, trim = pc.taps, None
     if ZTRIM and pc._w_cube is not None:
         lo, hi = ztrim_range(Z, Zo, pc.stride, pc.pad)
@@ -611,17 +660,18 @@ def conv_rows_wino(x, pc, out, relu, res, plan, in_ranges=None, twin=False):
                 else:
                     call("coocc_wino_input_strided", src, x.stride, x.B, x.X, x.Y, x.Z, cr, tile, dst, pc.Cin, G)
                 voff += cr
-    d = conv_desc(dev, in_=ptr(V), w=ptr(wp), out=ptr(Mb), M=pts * G, Cin=pc.Cin, Cout=pc.Cout, taps=3,
+    kz = pc.wino_kz           # the z taps stay direct: 3, or 1 for a 3x3x1 layer (the grouped GEMM is then pointwise)
+    d = conv_desc(dev, in_=ptr(V), w=ptr(wp), out=ptr(Mb), M=pts * G, Cin=pc.Cin, Cout=pc.Cout, taps=kz,
                   in_stride=pc.Cin, out_stride=pc.Cout, B=pts * G // x.Z, Xi=1, Yi=1, Zi=x.Z, Xo=1, Yo=1, Zo=x.Z,
-                  ksize=3, stride=1, pad=1, kx=1, ky=1, kz=3, pz=1, wgroup_rows=G, splitk=1, tile_hint=hint or TILE_HINT)
-    flops = 2.0 * pts * rows * pc.Cin * pc.Cout * 3
+                  ksize=3, stride=1, pad=1, kx=1, ky=1, kz=kz, pz=kz // 2, wgroup_rows=G, splitk=1, tile_hint=hint or TILE_HINT)
+    flops = 2.0 * pts * rows * pc.Cin * pc.Cout * kz
     if h2:
         d.mfma_dtype, d.alpha = 3, 1.0 / vscale
         if sdev is not None:
             d.alpha_dev = ptr(sdev, offset=1)
         launch_conv(d, V.device, "k_gemm_h2z wino%d" % tile, flops)
     else:
-        launch_conv(d, V.device, lambda: conv_kernel_name(pts * G, pc.Cout, False, hint, 3 * -(-pc.Cin // 32), grouped=True)
+        launch_conv(d, V.device, lambda: conv_kernel_name(pts * G, pc.Cout, False, hint, kz * -(-pc.Cin // 32), grouped=True)
                     + " wino%d" % tile, flops)
     tw = None
     if twin and h2 and pc.Cout % 32 == 0 and out.coff == 0 and out.stride % 4 == 0:
@@ -661,11 +711,16 @@ def out_dim(n, k, s, p):
     return (n + 2 * p - k) // s + 1
 
 
+def out_dims(X, Y, Z, pc):
+    """Output grid of layer ``pc`` on an [X, Y, Z] input (per-axis kernel / stride / padding)."""
+    return tuple(out_dim(n, k, s, p) for n, k, s, p in zip((X, Y, Z), pc.kernel, pc.strides, pc.pads))
+
+
 def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_for=()):
     """out = epi(conv(x)) on Rows.  res: Rows added before ReLU (res_mode 1).  ``twin_for``: the layers (PackedConv) that
     read the result next -- when one of them takes the split-f16 direct path the epilogue writes the H2 twin it needs
     (``out.h2``) next to the fp32 rows, which replaces that layer's conversion pass."""
-    Xo, Yo, Zo = (out_dim(n, pc.ksize, pc.stride, pc.pad) for n in (x.X, x.Y, x.Z))
+    Xo, Yo, Zo = out_dims(x.X, x.Y, x.Z, pc)
     M = x.B * Xo * Yo * Zo
     if out is None:
         out = Rows(torch.empty(M, pc.Cout, device=x.t.device, dtype=_F32), x.B, Xo, Yo, Zo, pc.Cout)
@@ -685,7 +740,9 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
     if trim is not None:
         # z taps lo..hi only: the others read nothing but padding on this grid
         d.kx, d.ky, d.kz, d.px, d.py, d.pz = 3, 3, trim[1] - trim[0] + 1, pc.pad, pc.pad, pc.pad - trim[0]
-    same = pc.stride == 1 and (Xo, Yo, Zo) == (x.X, x.Y, x.Z)
+    if pc.aniso:
+        (d.kx, d.ky, d.kz), (d.px, d.py, d.pz), (d.sx, d.sy, d.sz) = pc.kernel, pc.pads, pc.strides
+    same = pc.is_unit_stride and (Xo, Yo, Zo) == (x.X, x.Y, x.Z)
     flops = 2.0 * M * pc.Cin * pc.Cout * taps
     if family == "f16" and out.coff == 0 and out.stride == pc.Cout:
         # configs[4]'s reduced-precision path: ONE v_mfma_f32_32x32x16_f16 per step on f16 operands that live in HBM as f16 rows
@@ -734,7 +791,7 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
         d.in_, d.in_stride, d.mfma_dtype = x.data(), x.stride, 1 if bf16 else 0
         d.w = ptr(pc.ztrim_pack(*trim) if trim is not None else pc.w)
         name = "k_conv_bf16" if bf16 else lambda: conv_kernel_name(M, pc.Cout, False, 0, taps * -(-pc.Cin // 32),
-                                                                   pc.ksize == 1 and pc.stride == 1 and pc.pad == 0)
+                                                                   pc.is_pointwise)
     launch_conv(d, pc.w.device, name, flops)
     return out
 

@@ -78,9 +78,9 @@ __global__ __launch_bounds__(256, 2) void k_conv(ConvK p) {
       int oy = r % p.Yo; r /= p.Yo;
       int ox = r % p.Xo; int b = r / p.Xo;
       rbase[a] = ok ? b : -1;
-      rix[a] = ox * p.stride - p.px;
-      riy[a] = oy * p.stride - p.py;
-      riz[a] = oz * p.stride - p.pz;
+      rix[a] = ox * p.sx - p.px;
+      riy[a] = oy * p.sy - p.py;
+      riz[a] = oz * p.sz - p.pz;
     }
   }
 
@@ -257,9 +257,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf16(ConvK p) {
     int oy = r % p.Yo; r /= p.Yo;
     int ox = r % p.Xo; int b = r / p.Xo;
     rbase[a] = ok ? b : -1;
-    rix[a] = ox * p.stride - p.px;
-    riy[a] = oy * p.stride - p.py;
-    riz[a] = oz * p.stride - p.pz;
+    rix[a] = ox * p.sx - p.px;
+    riy[a] = oy * p.sy - p.py;
+    riz[a] = oz * p.sz - p.pz;
   }
   // iterations of the fp32 pack are 32-channel chunks ordered (channel chunk, tap); one K step here = two of them
   const int it0 = blockIdx.y * p.iters_per_split;
@@ -419,9 +419,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf16w(ConvK p) {
     int oz = m % p.Zo; int q = m / p.Zo;
     int oy = q % p.Yo; q /= p.Yo;
     int ox = q % p.Xo; int b = q / p.Xo;
-    rix[j] = m < p.M ? ox * p.stride - p.px : -(1 << 20);
-    riy[j] = oy * p.stride - p.py;
-    riz[j] = oz * p.stride - p.pz;
+    rix[j] = m < p.M ? ox * p.sx - p.px : -(1 << 20);
+    riy[j] = oy * p.sy - p.py;
+    riz[j] = oz * p.sz - p.pz;
     const unsigned qo = (unsigned)((slot ^ ((r >> 1) & 7)) * 16);
     abase[j] = ((((long long)b * p.Xi + rix[j]) * p.Yi + riy[j]) * p.Zi + riz[j]) * rowbytes + qo;
   }
@@ -798,9 +798,9 @@ __global__ __launch_bounds__(256, MINW) void k_conv2(ConvK p) {
     int oy = r % p.Yo; r /= p.Yo;
     int ox = r % p.Xo; int b = r / p.Xo;
     bool ok = m < p.M;
-    cx[a] = ok ? ox * p.stride - p.px : -4096;
-    cy[a] = oy * p.stride - p.py;
-    cz[a] = oz * p.stride - p.pz;
+    cx[a] = ok ? ox * p.sx - p.px : -4096;
+    cy[a] = oy * p.sy - p.py;
+    cz[a] = oz * p.sz - p.pz;
     rrow[a] = ((b * p.Xi + cx[a]) * p.Yi + cy[a]) * p.Zi + cz[a];
   }
   // Tile-relative addressing: input rows are visited in the lexicographic order of the outputs, so every row this
@@ -811,7 +811,7 @@ __global__ __launch_bounds__(256, MINW) void k_conv2(ConvK p) {
     int oz = m0 % p.Zo; int r = m0 / p.Zo;
     int oy = r % p.Yo; r /= p.Yo;
     int ox = r % p.Xo; int b = r / p.Xo;
-    int row0 = ((b * p.Xi + ox * p.stride - p.px) * p.Yi + oy * p.stride - p.py) * p.Zi + oz * p.stride - p.pz;
+    int row0 = ((b * p.Xi + ox * p.sx - p.px) * p.Yi + oy * p.sy - p.py) * p.Zi + oz * p.sz - p.pz;
     row0 = max(row0, 0);
 #pragma unroll
     for (int a = 0; a < PA; ++a) rrow[a] -= row0;
@@ -1241,6 +1241,8 @@ extern "C" int coocc_conv_fwd(const coocc_conv_desc* d, void* stream) {
   k.in_stride = d->in_stride; k.out_stride = d->out_stride; k.res_stride = d->res_stride;
   k.Xi = d->Xi; k.Yi = d->Yi; k.Zi = d->Zi; k.Xo = d->Xo; k.Yo = d->Yo; k.Zo = d->Zo;
   k.stride = d->stride;
+  COOCC_CHECK_ARG(d->sx >= 0 && d->sy >= 0 && d->sz >= 0, "conv_fwd: negative per-axis stride");
+  k.sx = d->sx > 0 ? d->sx : d->stride; k.sy = d->sy > 0 ? d->sy : d->stride; k.sz = d->sz > 0 ? d->sz : d->stride;
   if (d->kx > 0) { k.kx = d->kx; k.ky = d->ky; k.kz = d->kz; k.px = d->px; k.py = d->py; k.pz = d->pz; }
   else { k.kx = k.ky = k.kz = d->ksize; k.px = k.py = k.pz = d->pad; }
   k.wgroup_rows = d->wgroup_rows;
@@ -1364,8 +1366,13 @@ extern "C" int coocc_conv_fwd(const coocc_conv_desc* d, void* stream) {
   static const int v2mode = getenv("COOCC_CONV_V2") ? atoi(getenv("COOCC_CONV_V2")) : 1;
   const unsigned long long in_bytes = (unsigned long long)d->B * d->Xi * d->Yi * d->Zi * d->in_stride * 4ull;
   const unsigned long long w_bytes = (unsigned long long)k.taps * k.kchunks * k.Npad * KC * 4ull;
-  // rows a tile can touch above its first one (bound: stride-2 outputs advance the input rows up to 8x faster)
-  const unsigned long long window_rows = 8ull * 160 + (unsigned long long)k.kx * d->Yi * d->Zi + (unsigned long long)k.ky * d->Zi + k.kz + 8;
+  // rows a tile can touch above its first one: outputs are visited in (x, y, z) order, so a tile of <= 160 of them advances by sz rows
+  // per output inside a z line, by sy * Zi rows at each of the <= 160 / Zo + 2 y steps it crosses and by sx * Yi * Zi rows at each of
+  // the <= 160 / (Yo * Zo) + 2 x steps; the taps add the kernel's own extent
+  const unsigned long long yz_out = (unsigned long long)(d->Yo > 0 ? d->Yo : 1) * (d->Zo > 0 ? d->Zo : 1);
+  const unsigned long long window_rows = 160ull * k.sz + (160ull / (d->Zo > 0 ? d->Zo : 1) + 2) * k.sy * d->Zi +
+                                         (160ull / yz_out + 2) * k.sx * d->Yi * d->Zi +
+                                         (unsigned long long)k.kx * d->Yi * d->Zi + (unsigned long long)k.ky * d->Zi + k.kz + 8;
   const bool window_ok = window_rows * d->in_stride * 4ull < 0xFFFFFF00ull && (long long)d->B * d->Xi * d->Yi * d->Zi < (1ll << 31);
   // row-table mode on the pipelined kernel (128-row tiles, table slice in LDS).  The caller states the number of input
   // rows in B*Xi*Yi*Zi (1 = unknown -> phase-structured kernel); 32-bit row offsets need the input below 4 GB

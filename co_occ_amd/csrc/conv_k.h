@@ -9,6 +9,7 @@ struct ConvK {
   int M, Cin, Cout, Npad, taps, kchunks;
   int in_stride, out_stride, res_stride;
   int Xi, Yi, Zi, Xo, Yo, Zo, stride;
+  int sx, sy, sz;               // per-axis strides the geometric-tap kernels step by (= stride unless the descriptor names its own)
   int kx, ky, kz, px, py, pz;   // per-axis kernel extent / padding (taps = kx*ky*kz, tap index t = (dx*ky + dy)*kz + dz)
   int wgroup_rows;              // > 0: output rows [g*wgroup_rows, (g+1)*wgroup_rows) use weight pack g (Winograd points)
   size_t wgroup_floats;         // floats per weight pack

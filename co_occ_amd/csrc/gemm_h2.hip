@@ -472,9 +472,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_h2w(ConvK p) {
       int oz = m % p.Zo; int q = m / p.Zo;
       int oy = q % p.Yo; q /= p.Yo;
       int ox = q % p.Xo; const int b = q / p.Xo;
-      rix[j] = m < p.M ? ox * p.stride - p.px : -(1 << 20);
-      riy[j] = oy * p.stride - p.py;
-      riz[j] = oz * p.stride - p.pz;
+      rix[j] = m < p.M ? ox * p.sx - p.px : -(1 << 20);
+      riy[j] = oy * p.sy - p.py;
+      riz[j] = oz * p.sz - p.pz;
       rrow[j] = ((b * Xi + rix[j]) * Yi + riy[j]) * Zi + riz[j];
     }
   }
@@ -956,7 +956,7 @@ int coocc_launch_h2(ConvK& k, const coocc_conv_desc* d, hipStream_t s) {
   // stride-1 "same" geometry with <= 3 z taps: one LDS image per (chunk, dx, dy) serves the z taps (k_gemm_h2z); everything else
   // (strided, 1x1x1, row tables) one image per (chunk, tap) (k_gemm_h2w)
   const bool zshare = !table && !d->out_rows && !d->M_dev && k.stride == 1 && k.Xo == k.Xi && k.Yo == k.Yi && k.Zo == k.Zi && k.kz >= 1 && k.kz <= 3 &&
-                      k.taps > 1;
+                      (k.taps > 1 || d->wgroup_rows > 0);      // one z tap with weight groups: the Winograd-domain GEMM of a 3x3x1 layer
   COOCC_CHECK_ARG(zshare || d->wgroup_rows == 0, "conv_fwd: weight groups need the stride-1 same geometry");
   k.kchunks = d->Cin / kc;
   k.total_iters = k.taps * k.kchunks;

@@ -607,25 +607,63 @@ class COOCC_Ray(nn.Module):
 @DETECTORS.register_module()
 class COOCC_Ray_L(COOCC_Ray):
     """LiDAR-only variant (P/coocc/detectors/coocc_ray_lidar.py): same decoder and depth-only render regulariser (no
-    rgb head, :111-112; depth ground truth at gt_depths[-2], :507).  Its ``pts_backbone`` / ``pts_neck`` (SECOND3D /
-    SECOND3DFPN over a SparseEncoderHD volume, projects/configs/coocc_nusc/coocc_lidar.py) are upstream of the hot path and
-    resolved like the image encoder of COOCC_Ray (mmdet3d registries, injected modules, or ``external_encoders``)."""
+    rgb head, :111-112; depth ground truth at gt_depths[-2], :507).  Its dense trunk ``pts_backbone`` / ``pts_neck`` (SECOND3D /
+    SECOND3DFPN, projects/configs/coocc_nusc/coocc_lidar.py) is built from the unchanged config through this package's
+    registries and runs on the HIP engine (``lidar_trunk``).  The ``SparseEncoderHD`` middle encoder in front of it (spconv) stays
+    upstream and is resolved like the image encoder of COOCC_Ray (mmdet3d registries, injected modules, or
+    ``external_encoders``); ``precomputed=dict(pts_middle_feats=...)`` (its dense [B,C,Z,Y,X] output) runs the trunk without it."""
     WITH_RGB_HEAD = False
     DEPTH_GT_INDEX = -2
 
+    def trunk_from_middle(self, x):
+        """SparseEncoderHD's dense output [B,C,Z,Y,X] (a tensor, Rows, or a view that remembers them) -> (pts_voxel_feats
+        [1,C,X,Y,Z], [trunk output [B,C,Z,Y,X]]) (coocc_ray_lidar.py:249-256).  With both trunk modules of this package the whole
+        trunk stays on channels-last rows: one entry transposition at most, no conversion towards the fuser / encoder."""
+        from . import lidar_trunk as lt
+        if isinstance(self.pts_backbone, lt.SECOND3D) and isinstance(self.pts_neck, lt.SECOND3DFPN):
+            rows = lt.run_trunk(self.pts_backbone, self.pts_neck, x)
+            return rows.as_ncdhw(), [lt.rows_as_bczyx(rows)]
+        if self.pts_backbone is not None:
+            x = self.pts_backbone(x)
+        if self.pts_neck is not None:
+            x = self.pts_neck(x)
+        rows = lt.rows_of_bczyx(x) if torch.is_tensor(x) else None
+        return (rows.as_ncdhw() if rows is not None else x.permute(0, 1, 4, 3, 2)), [x]
+
     def extract_pts_feat(self, pts):
         """coocc_ray_lidar.py:236-256: the dense LiDAR trunk returns [B,C,Z,Y,X]; the detector permutes to [B,C,X,Y,Z]."""
-        if self.pts_middle_encoder is None or (self.pts_backbone is None and self.pts_neck is None):
-            raise NotImplementedError("COOCC_Ray_L: the LiDAR trunk (pts_middle_encoder / pts_backbone / pts_neck) is upstream of "
-                                      "the hot path and was not attached; feed precomputed=dict(pts_voxel_feats=...)")
+        if self.pts_backbone is None and self.pts_neck is None:
+            raise NotImplementedError("COOCC_Ray_L was built without pts_backbone / pts_neck (SECOND3D / SECOND3DFPN)")
+        if self.pts_middle_encoder is None:
+            raise NotImplementedError("COOCC_Ray_L: the sparse middle encoder (SparseEncoderHD, spconv) is upstream of the hot path "
+                                      "and was not attached; assign model.pts_middle_encoder, or feed its dense output as "
+                                      "precomputed=dict(pts_middle_feats=...) (or the trunk's as pts_voxel_feats=...)")
         if isinstance(pts, (list, tuple)):
             assert len(pts) == 1, "batch size 1 (hard-coded upstream)"
             pts = pts[0]
         voxels, coors, num_points = self.pts_voxel_layer(pts)
         feats = self.pts_voxel_encoder(voxels, num_points, coors)
-        x = self.pts_middle_encoder(feats, coors, 1)
-        if self.pts_backbone is not None:
-            x = self.pts_backbone(x)
-        if self.pts_neck is not None:
-            x = self.pts_neck(x)
-        return x.permute(0, 1, 4, 3, 2), [x]
+        return self.trunk_from_middle(self.pts_middle_encoder(feats, coors, 1))
+
+    def _with_trunk(self, precomputed):
+        """``precomputed`` with ``pts_middle_feats`` (the middle encoder's dense output) run through the trunk into ``pts_voxel_feats``."""
+        if precomputed is not None and precomputed.get("pts_middle_feats") is not None and precomputed.get("pts_voxel_feats") is None:
+            precomputed = dict(precomputed)
+            precomputed["pts_voxel_feats"] = self.trunk_from_middle(precomputed.pop("pts_middle_feats"))[0]
+        return precomputed
+
+    def serving_frame(self, img=None, points=None, img_metas=None, precomputed=None):
+        return super().serving_frame(img, points, img_metas, self._with_trunk(precomputed))
+
+    def forward_train(self, points=None, img_metas=None, img_inputs=None, gt_occ=None, points_occ=None, visible_mask=None,
+                      gt_depths=None, precomputed=None, generator=None, **kwargs):
+        if precomputed is not None and precomputed.get("pts_middle_feats") is not None:
+            raise NotImplementedError("COOCC_Ray_L.forward_train: precomputed pts_middle_feats would run SECOND3D / SECOND3DFPN in "
+                                      "training mode, which is not built; feed pts_voxel_feats")
+        return super().forward_train(points, img_metas, img_inputs, gt_occ, points_occ, visible_mask, gt_depths, precomputed,
+                                     generator, **kwargs)
+
+    def simple_test(self, img_metas=None, img=None, gt_depths=None, points=None, rescale=False, points_occ=None,
+                    gt_occ=None, visible_mask=None, precomputed=None):
+        return super().simple_test(img_metas, img, gt_depths, points, rescale, points_occ, gt_occ, visible_mask,
+                                   self._with_trunk(precomputed))

@@ -195,3 +195,65 @@ def lidar_points(n=280000, seed=8):
     r = torch.rand(n, generator=g) ** 0.5 * 50
     th = torch.rand(n, generator=g) * 6.2832
     return torch.stack([r * torch.cos(th), r * torch.sin(th), torch.randn(n, generator=g) * 0.8 - 1.5, torch.rand(n, generator=g)], 1)
+
+
+# ------------------------------------------------------------------ the LiDAR-only trunk (SECOND3D + SECOND3DFPN)
+# name: input grid (Z, Y, X) of the [1,C,Z,Y,X] volume, layer_nums, seed.  "config": the layer counts of coocc_lidar.py;
+# "full": the config's own grid (the 100x100x8 volume the decoder consumes)
+SECOND3D_CASES = {
+    "small": dict(grid_zyx=(2, 8, 8), layer_nums=(1, 1, 1), seed=61),
+    "config": dict(grid_zyx=(2, 16, 16), layer_nums=(5, 5, 5), seed=62),
+    "full": dict(grid_zyx=(8, 100, 100), layer_nums=(5, 5, 5), seed=63),
+}
+
+
+def second3d_cfg(layer_nums=(5, 5, 5)):
+    """(pts_backbone, pts_neck) of projects/configs/coocc_nusc/coocc_lidar.py:113-131 (``layer_nums`` is the config's [5,5,5])."""
+    norm = dict(type='BN3d', eps=1e-3, momentum=0.01)
+    backbone = dict(type='SECOND3D', in_channels=[128, 128, 128], out_channels=[128, 256, 512], layer_nums=list(layer_nums),
+                    layer_strides=[1, 2, 4], is_cascade=False, norm_cfg=dict(norm),
+                    conv_cfg=dict(type='Conv3d', kernel=(1, 3, 3), bias=False))
+    neck = dict(type='SECOND3DFPN', in_channels=[128, 256, 512], out_channels=[128, 128, 128], upsample_strides=[1, 2, 4],
+                norm_cfg=dict(norm), upsample_cfg=dict(type='deconv3d', bias=False),
+                extra_conv=dict(type='Conv3d', num_conv=3, bias=False), use_conv_for_no_stride=True)
+    return backbone, neck
+
+
+def second3d_input(grid_zyx, C=128, seed=61, p=0.35):
+    """A dense LiDAR volume [1,C,Z,Y,X] as a sparse encoder's ``.dense()`` leaves it: non-negative, zero outside the occupied voxels."""
+    Z, Y, X = grid_zyx
+    g = _rng(seed, "second3d")
+    x = np.maximum(g.standard_normal((1, C, Z, Y, X), dtype=np.float32), 0)
+    x *= (g.random((1, 1, Z, Y, X)) < p)
+    return torch.from_numpy(x.astype(np.float32))
+
+
+def second3d_weights(backbone, neck, seed):
+    """Seeded state_dicts for a (SECOND3D, SECOND3DFPN) pair (any implementation with the reference's keys): Kaiming-normal
+    weights, BN weight / variance U(0.5, 1.5), mean / bias N(0, 0.1) (``random_state_dict``)."""
+    return random_state_dict(backbone.state_dict(), seed), random_state_dict(neck.state_dict(), seed + 1)
+
+
+def model_cfg_lidar(rendering=False):
+    """The hot-path slice of projects/configs/coocc_nusc/coocc_lidar.py:76-190 (``COOCC_Ray_L``): no fuser, no view transformer;
+    SparseEncoderHD -> SECOND3D -> SECOND3DFPN -> CustomResNet3D -> FPN3D -> OccHead (no image branch in the fine head)."""
+    bn = dict(type='SyncBN', requires_grad=True)
+    backbone, neck = second3d_cfg()
+    return dict(
+        type='COOCC_Ray_L', use_rendering=rendering, test_rendering=False, empty_idx=0, scale=4, nerf_density=True,
+        pts_voxel_layer=dict(max_num_points=10, point_cloud_range=[-50, -50, -5.0, 50, 50, 3.0], voxel_size=[0.125] * 3,
+                             max_voxels=(90000, 120000)),
+        pts_voxel_encoder=dict(type='HardSimpleVFE', num_features=5),
+        pts_middle_encoder=dict(type='SparseEncoderHD', in_channels=4, sparse_shape=[65, 800, 800], output_channels=128,
+                                order=('conv', 'norm', 'act'),
+                                encoder_channels=((16, 16, 32), (32, 32, 64), (64, 64, 128), (128, 128)),
+                                encoder_paddings=((0, 0, 1), (0, 0, 1), (0, 0, [0, 1, 1]), (0, 0)), block_type='basicblock',
+                                fp16_enabled=False),
+        pts_backbone=backbone, pts_neck=neck,
+        semantic_encoder=dict(type='CustomResNet3D', depth=18, n_input_channels=128, block_inplanes=[128, 256, 512, 1024],
+                              out_indices=(0, 1, 2, 3), norm_cfg=bn),
+        semantic_neck=dict(type='FPN3D', with_cp=True, in_channels=[128, 256, 512, 1024], out_channels=256, norm_cfg=bn),
+        pts_bbox_head=dict(type='OccHead', norm_cfg=bn, soft_weights=True, cascade_ratio=2, sample_from_voxel=False,
+                           sample_from_img=False, final_occ_size=[200, 200, 16], fine_topk=15000, empty_idx=0, num_level=4,
+                           in_channels=[256] * 4, out_channel=17, point_cloud_range=[-50, -50, -5.0, 50, 50, 3.0]),
+    )

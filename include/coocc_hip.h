@@ -259,6 +259,9 @@ typedef struct coocc_conv_desc {
   const float* alpha_dev; /* mfma_dtype 3 / 4: the accumulators are also multiplied by *alpha_dev, read on the device -- the inverse of an
                              operand scale that a kernel chose (coocc_conv_epilogue_bwd_ex: the gradient operand of the training
                              path's dgrad GEMMs); NULL = none */
+  int sx, sy, sz;         /* geometric taps: per-axis strides, input coordinate = output coordinate * s - p (0 = `stride`).  The
+                             (1,s,s) strides of SECOND3D's first block convs (second3d.py:58, kernel (1,3,3) over [B,C,Z,Y,X]) are
+                             sx = sy = s, sz = 1 in this library's (x, y, z) row order; `stride` then only has to differ from 1 */
 } coocc_conv_desc;
 
 /* nn.Conv3d(k=3|1)+BN(eval)+ReLU(+residual) (bifuser_n.py:23-30, resnet3d.py:34-64,
@@ -795,6 +798,25 @@ int coocc_sparse_down_flags(const int32_t* coors, int M, int ksize, int stride, 
 /* linear ids (z*H + y)*W + x -> coors:[n,3] and (optionally) the channels-last rows (x*H + y)*D + z of the dense volume */
 int coocc_sparse_lin_to_coors(const int32_t* lin, int n, int D, int H, int W, int32_t* coors, int32_t* dense_rows,
                               void* stream);
+
+/* ---------------------------------------------------------------- LiDAR-only trunk (SECOND3D + SECOND3DFPN) */
+
+/* sum(ups) of SECOND3DFPN.forward (P/coocc/necks/second3d_fpn.py:119-122) over the outputs of its deblocks
+ * (nn.ConvTranspose3d(kernel = stride = (1,s,s)) + BN3d + ReLU, :47-69).  Such a deconvolution has no overlap, so each deblock
+ * runs as a pointwise coocc_conv_fwd Cin -> s*s*Cout on its COARSE rows (weights packed [(kx*s + ky)*Cout + co][ci], BN scale /
+ * bias repeated per child, ReLU in the epilogue) and this entry point gathers the children:
+ *   out[b,x,y,z,:] = ((0 + U0[..]) + U1[b, x/s1, y/s1, z, (x%s1)*s1 + y%s1, :]) + U2[...]     (the reference's order of additions)
+ * ups / strides: HOST arrays of `levels` (1-4) device pointers / strides (1, 2, 4, 8); level l holds
+ * [B*(X/s)*(Y/s)*Z][s*s][C] floats; X, Y multiples of every stride (the levels are of equal size after upsampling, as sum()
+ * requires).  out: [B*X*Y*Z][out_stride] rows in (b,x,y,z) order; out_h2_twin: optional H2 copy [rows][C] (C % 32 == 0) for a
+ * split-f16 consumer outside the Winograd path.  C % 4 == 0. */
+int coocc_fpn_sum(const float* const* ups, const int* strides, int levels, int B, int X, int Y, int Z, int C, float* out,
+                  int out_stride, void* out_h2_twin, void* stream);
+/* The reference's dense LiDAR volume [B,C,Z,Y,X] (SparseEncoderHD's .dense() output, the input of SECOND3D.forward,
+ * P/coocc/backbones/second3d.py:91-104) -> channels-last rows [B*X*Y*Z][dst_stride] (channels at dst_coff) in (b,x,y,z) order,
+ * one pass: replaces x.permute(0,1,4,3,2).contiguous() + coocc_ncdhw_to_ndhwc.  C, dst_stride, dst_coff % 4 == 0. */
+int coocc_zyx_to_rows(const float* src, float* dst, int B, int C, int Z, int Y, int X, int dst_stride, int dst_coff,
+                      void* stream);
 
 #ifdef __cplusplus
 }
