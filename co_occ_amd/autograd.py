@@ -6,13 +6,11 @@ channels-last rows, the G1 row gather, voxel pooling / fused lift-splat, the R2 
 the FPN trilinear upsample-add.  Indices (FPS / ball / top-K / assignment, voxel keys) are
 non-differentiable, as upstream.  Every backward is a HIP kernel; nothing falls back to torch ops.
 """
-import ctypes
-
 import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .core import TILE_HINT, conv_desc, launch_conv, out_dim, workspace, ztrim_range
+from .core import TILE_HINT, conv_desc, launch_conv, lib_pack, out_dim, stream_buffer, workspace, ztrim
 
 _F32 = torch.float32
 _tables = {}
@@ -37,16 +35,12 @@ TRAIN_H2_GRAD_TARGET = 1024.0
 # 1x1x1 / Linear layers, both operands rewritten voxel-major (KH2), the gradient one with the same device-chosen scale.
 # COOCC_TRAIN_H2_WGRAD=0: the fp32-MFMA k_wgrad.
 TRAIN_H2_WGRAD = TRAIN_H2 and __import__("os").environ.get("COOCC_TRAIN_H2_WGRAD", "1") != "0"
-_amax_words = {}
 
 
 def _amax_word(dev):
     """The zeroed words (COOCC_AMAX_WORDS) coocc_conv_epilogue_bwd_ex collects max |dacc| in (left zero by its second kernel); one
     set per stream."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _amax_words:
-        _amax_words[key] = torch.zeros(2048, device=dev, dtype=torch.int32)
-    return _amax_words[key]
+    return stream_buffer(dev, "amax", 2048, torch.int32, zero=True)
 
 
 def _pad4(n):
@@ -107,29 +101,18 @@ def dgrad_classes(dev, B, Xi, Yi, Zi, ksize, stride, pad):
 
 def pack_weights_dev(w, Cout, Cin, taps, mode):
     """Device-side fragment-major packing (modes: 0 fwd, 1 fwd tap-major, 2 dgrad flipped, 3 dgrad)."""
-    lib = _lib.load()
-    w = w.detach().float().contiguous()
-    n = lib.coocc_conv_pack_weights_dev(None, Cout, Cin, taps, mode, None, None)
-    if n < 0:
-        _lib.check(int(n))
-    packed = torch.empty(n, dtype=_F32, device=w.device)
-    n = lib.coocc_conv_pack_weights_dev(ptr(w), Cout, Cin, taps, mode, ptr(packed), _lib.stream(w.device))
-    if n < 0:
-        _lib.check(int(n))
-    return packed
+    return lib_pack("coocc_conv_pack_weights_dev", w.detach().float().contiguous(), Cout, Cin, taps, mode)
 
 
 def pack_weights_h2_dev(w, Cout, Cin, taps, mode):
-    """``pack_weights_dev`` for the split-f16 engine (coocc_conv_pack_weights_h2_dev)."""
-    lib = _lib.load()
-    n = lib.coocc_conv_pack_weights_h2_dev(None, Cout, Cin, taps, mode, None, None)
-    if n < 0:
-        _lib.check(int(n))
-    packed = torch.empty(n, dtype=_F32, device=w.device)
-    n = lib.coocc_conv_pack_weights_h2_dev(ptr(w), Cout, Cin, taps, mode, ptr(packed), _lib.stream(w.device))
-    if n < 0:
-        _lib.check(int(n))
-    return packed
+    """``pack_weights_dev`` for the split-f16 engine."""
+    return lib_pack("coocc_conv_pack_weights_h2_dev", w, Cout, Cin, taps, mode)
+
+
+def _z_taps(w, lo, hi):
+    """The z taps lo..hi of 3x3x3 weights, [Cout, Cin, 9 * (hi - lo + 1)]."""
+    Cout, Cin = w.shape[:2]
+    return w.view(Cout, Cin, 3, 3, 3)[..., lo:hi + 1].contiguous().view(Cout, Cin, -1)
 
 
 def _h2_direct(K, flops):
@@ -144,51 +127,30 @@ def _rows_h2(x2d, C, scale_dev=None):
     return xh
 
 
-class _DevWinoF32:
+class _DevWino:
     """What core.conv_rows_wino needs of a PackedConv, with the Winograd packs transformed on the device from the live
-    parameter (training re-packs every step): forward packs, or (``dgrad``) the packs of dx = conv(dy, W')."""
+    parameter (training re-packs every step): forward packs, or (``dgrad``) the packs of dx = conv(dy, W').  ``h2``: the GEMM runs
+    on the split-f16 engine like inference's (core.h2_capable), on packs transformed + split on the device."""
 
-    def __init__(self, w5, dgrad, scale=None, bias=None):
+    def __init__(self, w5, dgrad, scale=None, bias=None, h2=False):
         Cout, Cin = w5.shape[:2]
         self.Cin, self.Cout = (Cout, Cin) if dgrad else (Cin, Cout)
-        self.scale, self.bias = scale, bias
+        self.scale, self.bias, self.h2 = scale, bias, h2
         self._w_raw, self.wino_tile = True, None
         self.wino_kz, self.aniso = 3, False       # 3x3x3 stride-1 layers only (core.conv_rows_wino)
         self._w5, self._dgrad, self._packs = w5, int(bool(dgrad)), {}
         self.operand_scale_dev = None         # split-f16 engine, dgrad: {scale, 1 / scale} of the gradient rows, chosen on the device
 
+    def _pack(self, entry, tile):
+        if (entry, tile) not in self._packs:
+            self._packs[entry, tile] = lib_pack(entry, self._w5, *self._w5.shape[:2], tile, self._dgrad).view((tile + 2) ** 2, -1)
+        return self._packs[entry, tile]
+
     def wino_pack(self, tile):
-        if tile not in self._packs:
-            lib = _lib.load()
-            Cout, Cin = self._w5.shape[:2]
-            n = lib.coocc_wino_pack_weights_dev(None, Cout, Cin, tile, self._dgrad, None, None)
-            if n < 0:
-                _lib.check(int(n))
-            packed = torch.empty((tile + 2) ** 2, n // (tile + 2) ** 2, dtype=_F32, device=self._w5.device)
-            n = lib.coocc_wino_pack_weights_dev(ptr(self._w5), Cout, Cin, tile, self._dgrad, ptr(packed), _lib.stream(self._w5.device))
-            if n < 0:
-                _lib.check(int(n))
-            self._packs[tile] = packed
-        return self._packs[tile]
+        return self._pack("coocc_wino_pack_weights_dev", tile)
 
-
-class _DevWino(_DevWinoF32):
     def wino_h2_pack(self, tile):
-        """The same packs for the split-f16 engine (csrc/gemm_h2.hip), transformed + split on the device from the live parameter:
-        training's Winograd forward / dgrad GEMMs run on the f16 matrix cores like inference's (core.h2_capable)."""
-        key = ("h2", tile)
-        if key not in self._packs:
-            lib = _lib.load()
-            Cout, Cin = self._w5.shape[:2]
-            n = lib.coocc_wino_pack_weights_h2_dev(None, Cout, Cin, tile, self._dgrad, None, None)
-            if n < 0:
-                _lib.check(int(n))
-            packed = torch.empty((tile + 2) ** 2, n // (tile + 2) ** 2, dtype=_F32, device=self._w5.device)
-            n = lib.coocc_wino_pack_weights_h2_dev(ptr(self._w5), Cout, Cin, tile, self._dgrad, ptr(packed), _lib.stream(self._w5.device))
-            if n < 0:
-                _lib.check(int(n))
-            self._packs[key] = packed
-        return self._packs[key]
+        return self._pack("coocc_wino_pack_weights_h2_dev", tile)
 
 
 def _wino_train(x2d, geom, w5, dgrad, out2d, scale, shift, res2d, relu, grad_scale=None):
@@ -198,7 +160,7 @@ def _wino_train(x2d, geom, w5, dgrad, out2d, scale, shift, res2d, relu, grad_sca
     if not TRAIN_WINO:
         return False
     B, X, Y, Z = geom
-    pk = (_DevWino if ((TRAIN_H2_DGRAD and grad_scale is not None) if dgrad else TRAIN_H2) else _DevWinoF32)(w5, dgrad, scale, shift)
+    pk = _DevWino(w5, dgrad, scale, shift, h2=(TRAIN_H2_DGRAD and grad_scale is not None) if dgrad else TRAIN_H2)
     pk.operand_scale_dev = grad_scale if dgrad else None
     xr = core.Rows(x2d, B, X, Y, Z, pk.Cin)
     plan = core.wino_plan(xr, pk, out2d.shape[0], 1 if res2d is not None else 0)
@@ -226,7 +188,7 @@ def _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw, gscale=None):
     B, X, Y, Z = geom
     dev = x2d.device
     xr = core.Rows(x2d, B, X, Y, Z, Cin)
-    pk = _DevWinoF32(torch.empty(Cout, Cin, 0, device=dev), False)      # geometry only: no packs are made (fp32 V / dM rows)
+    pk = _DevWino(torch.empty(Cout, Cin, 0, device=dev), False)      # geometry only: no packs are made (fp32 V / dM rows)
     plan = core.wino_plan(xr, pk, x2d.shape[0], 0)
     if plan is None:
         return False
@@ -301,12 +263,10 @@ class ConvRowsFn(torch.autograd.Function):
         w_ = weight.detach().float().contiguous()
         if not (ksize == 3 and stride == 1 and pad == 1 and
                 _wino_train(x2d, geom, w_.view(Cout, Cin, 3, 3, 3), False, out, scale, eff_shift, res2d, relu)):
-            kd, wsub, nt = None, w_.reshape(Cout, Cin, taps), taps
-            if ksize == 3:
-                lo, hi = ztrim_range(Zi, Zo, stride, pad)
-                if hi - lo < 2:         # z taps that only read padding are dropped (exact)
-                    wsub = w_.view(Cout, Cin, 3, 3, 3)[..., lo:hi + 1].contiguous().view(Cout, Cin, -1)
-                    nt, kd = wsub.shape[2], (3, 3, hi - lo + 1, pad, pad, pad - lo)
+            wsub, nt = w_.reshape(Cout, Cin, taps), taps
+            trim, kd = ztrim(Zi, Zo, stride, pad) if ksize == 3 else (None, None)
+            if trim is not None:         # z taps that only read padding are dropped (exact)
+                wsub, nt = _z_taps(w_, *trim), 9 * kd[2]
             if _h2_direct(Cin, 2.0 * out.shape[0] * Cin * Cout * nt):
                 _conv_launch(_rows_h2(x2d, Cin), Cin, pack_weights_h2_dev(wsub, Cout, Cin, nt, 0), out, Cout, nt, geom, geom_out, ksize,
                              stride, pad, scale, eff_shift, res2d, relu, kdims=kd, h2_alpha=1.0)
@@ -355,12 +315,10 @@ class ConvRowsFn(torch.autograd.Function):
                                 None, False, grad_scale=gscale_d)):
                 pass
             elif stride == 1:
-                kd, wsub, nt, pd = None, w3, taps, ksize - 1 - pad
-                if ksize == 3:
-                    lo, hi = ztrim_range(geom_out[3], Zi, 1, pd)        # z taps of the flipped kernel that see real dy voxels
-                    if hi - lo < 2:
-                        wsub = weight.detach().float().view(Cout, Cin, 3, 3, 3)[..., 2 - hi:2 - lo + 1].contiguous().view(Cout, Cin, -1)
-                        nt, kd = wsub.shape[2], (3, 3, hi - lo + 1, pd, pd, pd - lo)
+                wsub, nt, pd = w3, taps, ksize - 1 - pad
+                trim, kd = ztrim(geom_out[3], Zi, 1, pd) if ksize == 3 else (None, None)    # z taps of the flipped kernel that see real dy voxels
+                if trim is not None:
+                    wsub, nt = _z_taps(weight.detach().float(), 2 - trim[1], 2 - trim[0]), 9 * kd[2]
                 if gscale_d is not None and _h2_direct(Cout, 2.0 * Mi * Cin * Cout * nt):
                     # the gradient operand scaled by gscale[0] (chosen on the device), undone by the GEMM through gscale[1]
                     _conv_launch(_rows_h2(dacc, Cout, gscale_d), Cout, pack_weights_h2_dev(wsub, Cout, Cin, nt, 2), dx, Cin,

@@ -10,12 +10,9 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, call, ptr
+from ._lib import TIMER, ConvDesc, KernelTimer, call, ptr  # noqa: F401  (KernelTimer: re-exported)
 
 _F32 = torch.float32
-
-
-from ._lib import TIMER, KernelTimer  # noqa: E402,F401
 
 
 TILE_HINT = int(__import__("os").environ.get("COOCC_CONV_TILE", "0"))   # 0 auto | 128 | 160 (tuning knob)
@@ -249,10 +246,31 @@ def deconv_weight(w, s):
     return w.detach()[:, :, 0].permute(3, 2, 1, 0).reshape(s * s * cout, cin).contiguous()
 
 
+def lib_pack(entry, w, *dims):
+    """The library's size-then-fill packing idiom: ``entry`` (one of the coocc_*pack_weights* entry points) is asked for the pack's
+    size in floats, then fills a fresh fp32 tensor of that size from the contiguous fp32 weights ``w``, on ``w``'s device -- a host
+    tensor through the host entry point, a HIP tensor through a ``_dev`` one on its current stream.  A negative return raises."""
+    fn = getattr(_lib.load(), entry)
+    if w.is_cuda:
+        src, tail = ptr(w), (_lib.stream(w.device),)
+    else:
+        src, tail = ctypes.c_void_p(w.data_ptr()), ()
+    n = fn(src, *dims, None, *(None,) * len(tail))
+    if n < 0:
+        _lib.check(int(n))
+    packed = torch.empty(n, dtype=_F32, device=w.device)
+    n = fn(src, *dims, ptr(packed) if w.is_cuda else ctypes.c_void_p(packed.data_ptr()), *tail)
+    if n < 0:
+        _lib.check(int(n))
+    return packed
+
+
 class PackedConv:
     """A conv/linear layer in the layout coocc_conv_fwd consumes (+ folded norm).  Cubic by default (``ksize`` / ``stride`` /
     ``pad``); ``kernel`` = (kx,ky,kz) with ``strides`` = (sx,sy,sz) and ``pads`` = (px,py,pz) describe an anisotropic layer
     (weight [Cout,Cin,kx,ky,kz]: ``zyx_weight`` of a reference [.,.,kz,ky,kx] one), e.g. SECOND3D's 3x3x1 convs."""
+
+    h2 = True                        # carries split-f16 packs (``h2_capable``)
 
     def __init__(self, weight, bn=None, bias=None, ksize=1, stride=1, pad=0, tap_major=False, taps=None, kernel=None,
                  strides=None, pads=None):
@@ -285,19 +303,12 @@ class PackedConv:
             self._w_raw, self.wino_kz = w, self.kernel[2]
         # cubic 3x3x3 weights also kept for the z-trimmed packs (conv_rows: taps that only ever see z padding)
         self._w_cube = w.view(self.Cout, self.Cin, 3, 3, 3) if (ksize == 3 and not tap_major and taps == 27 and not self.aniso) else None
-        self._ztrim = {}
-        self._wino = {}
-        self._bf16 = {}
+        self._packs = {}             # lazily built packs on the weight's device, keyed (family, z trim (lo, hi) | None | Winograd tile)
         # [Cout, Cin, taps] on the host: source of the bf16 / f16 packs (tap-major weights are [Cout, taps * Cin])
         self._w_taps = w if not tap_major else w.view(self.Cout, taps, self.Cin).permute(0, 2, 1).contiguous()
         self.wino_tile = None        # per-layer override of WINO_TILE (2 | 3 | 4)
-        lib = _lib.load()
-        n = lib.coocc_conv_pack_weights(ctypes.c_void_p(w.data_ptr()), self.Cout, self.Cin, taps, int(tap_major), None)
-        packed = torch.empty(n, dtype=_F32)
-        lib.coocc_conv_pack_weights(ctypes.c_void_p(w.data_ptr()), self.Cout, self.Cin, taps, int(tap_major),
-                                    ctypes.c_void_p(packed.data_ptr()))
         dev = weight.device
-        self.w = packed.to(dev)
+        self.w = lib_pack("coocc_conv_pack_weights", w, self.Cout, self.Cin, taps, int(tap_major)).to(dev)
         if bn is not None:
             s, b = fold_bn(bn, bias)
             self.scale, self.bias = s.to(dev).contiguous(), b.to(dev).contiguous()
@@ -322,36 +333,52 @@ class PackedConv:
         """1x1x1, stride 1, no padding: input row = output row."""
         return self.kernel == (1, 1, 1) and self.strides == (1, 1, 1) and self.pads == (0, 0, 0)
 
+    def _cached(self, key, build):
+        p = self._packs.get(key)
+        if p is None:
+            p = self._packs[key] = build().to(self.w.device)
+        return p
+
+    def _taps(self, trim=None):
+        """Host weights [Cout, Cin, taps]: every tap or, with ``trim`` = (lo, hi), the z taps lo..hi of a 3x3x3 kernel."""
+        if trim is None:
+            return self._w_taps
+        return self._w_cube[:, :, :, :, trim[0]:trim[1] + 1].reshape(self.Cout, self.Cin, -1).contiguous()
+
+    def _padded(self, w):
+        """``w`` [Cout, ...] with Cout zero-padded to a multiple of 128 (the GEMMs' N tile)."""
+        wp = torch.zeros(-(-self.Cout // 128) * 128, *w.shape[1:], dtype=w.dtype)
+        wp[:self.Cout] = w
+        return wp
+
     def ztrim_pack(self, lo, hi):
         """Pack of the z taps lo..hi only (3 x 3 x (hi-lo+1) kernel): the other z taps read nothing but padding
         for every output voxel of the grid this is called for, so dropping them is exact."""
-        if (lo, hi) not in self._ztrim:
-            w = self._w_cube[:, :, :, :, lo:hi + 1].contiguous().view(self.Cout, self.Cin, -1)
-            lib = _lib.load()
-            n = lib.coocc_conv_pack_weights(ctypes.c_void_p(w.data_ptr()), self.Cout, self.Cin, w.shape[2], 0, None)
-            packed = torch.empty(n, dtype=_F32)
-            lib.coocc_conv_pack_weights(ctypes.c_void_p(w.data_ptr()), self.Cout, self.Cin, w.shape[2], 0,
-                                        ctypes.c_void_p(packed.data_ptr()))
-            self._ztrim[(lo, hi)] = packed.to(self.w.device)
-        return self._ztrim[(lo, hi)]
+        def build():
+            return lib_pack("coocc_conv_pack_weights", self._taps((lo, hi)), self.Cout, self.Cin, 9 * (hi - lo + 1), 0)
+        return self._cached(("ztrim", (lo, hi)), build)
 
-    def bf16_pack(self, ztrim=None):
-        """bf16 pack of k_conv_bf16w (fragment-major, RNE), for all taps or, with
-        ``ztrim=(lo, hi)``, for the z taps lo..hi of a 3x3x3 kernel only.  None when the layer cannot take that kernel."""
+    def _frag64(self, dtype, trim):
+        """Fragment-major 16-bit pack, RNE: [(Cin/64 chunk, tap)][Npad/32][4 k16 steps][2 lane halves][32 columns][8 k]
+        (k = 64 chunk + 16 s + 8 h + e).  None when Cin % 64."""
         if self._w_taps is None or self.Cin % 64:
             return None
-        if ztrim not in self._bf16:
-            w = self._w_taps
-            if ztrim is not None:
-                w = self._w_cube[:, :, :, :, ztrim[0]:ztrim[1] + 1].reshape(self.Cout, self.Cin, -1)
-            taps = w.shape[2]
-            npad = -(-self.Cout // 128) * 128
-            wp = torch.zeros(npad, self.Cin, taps, dtype=_F32)
-            wp[:self.Cout] = w
-            # fragment-major: [(chunk, tap)][Npad/32][4 k-steps][2 lane halves][32 columns][8 k] (k = 16 s + 8 h + e)
-            pack = wp.view(npad // 32, 32, self.Cin // 64, 4, 2, 8, taps).permute(2, 6, 0, 3, 4, 1, 5)
-            self._bf16[ztrim] = pack.contiguous().to(torch.bfloat16).to(self.w.device)
-        return self._bf16[ztrim]
+
+        def build():
+            wp = self._padded(self._taps(trim))
+            # nt, li, chunk, s, hf, e, t -> chunk, t, nt, s, hf, li, e
+            pack = wp.view(wp.shape[0] // 32, 32, self.Cin // 64, 4, 2, 8, wp.shape[2]).permute(2, 6, 0, 3, 4, 1, 5)
+            return pack.contiguous().to(dtype)
+        return self._cached(("bf16" if dtype == torch.bfloat16 else "h1", trim), build)
+
+    def bf16_pack(self, ztrim=None):
+        """bf16 pack of k_conv_bf16w (``_frag64``), for all taps or, with ``ztrim=(lo, hi)``, for the z taps lo..hi of a 3x3x3
+        kernel only.  None when the layer cannot take that kernel."""
+        return self._frag64(torch.bfloat16, ztrim)
+
+    def h1_pack(self, ztrim=None):
+        """One-term f16 pack (mfma_dtype 4; ``_frag64``): all taps or the z taps lo..hi of a 3x3x3 kernel.  None when Cin % 64."""
+        return self._frag64(torch.float16, ztrim)
 
     @staticmethod
     def _h2_layout(w64):
@@ -372,53 +399,12 @@ class PackedConv:
         None when the layer cannot take the h2 kernel (Cin % 32)."""
         if self._w_taps is None or self.Cin % 32:
             return None
-        key = ("h2", ztrim)
-        if key not in self._bf16:
-            w = self._w_taps
-            if ztrim is not None:
-                w = self._w_cube[:, :, :, :, ztrim[0]:ztrim[1] + 1].reshape(self.Cout, self.Cin, -1)
-            npad = -(-self.Cout // 128) * 128
-            wp = torch.zeros(npad, self.Cin, w.shape[2], dtype=torch.float64)
-            wp[:self.Cout] = w.double()
-            self._bf16[key] = self._h2_layout(wp).to(self.w.device)
-        return self._bf16[key]
-
-    def h1_pack(self, ztrim=None):
-        """One-term f16 pack (mfma_dtype 4): [(Cin/64 chunk, tap)][Npad/32][4 k16 steps][64 lanes][8 f16], RNE; all taps or the z
-        taps lo..hi of a 3x3x3 kernel.  None when Cin % 64."""
-        if self._w_taps is None or self.Cin % 64:
-            return None
-        key = ("h1", ztrim)
-        if key not in self._bf16:
-            w = self._w_taps
-            if ztrim is not None:
-                w = self._w_cube[:, :, :, :, ztrim[0]:ztrim[1] + 1].reshape(self.Cout, self.Cin, -1)
-            taps = w.shape[2]
-            npad = -(-self.Cout // 128) * 128
-            wp = torch.zeros(npad, self.Cin, taps, dtype=_F32)
-            wp[:self.Cout] = w
-            # nt, li, chunk, s, hf, e, t -> chunk, t, nt, s, hf, li, e        (k = 64 chunk + 16 s + 8 hf + e)
-            pack = wp.view(npad // 32, 32, self.Cin // 64, 4, 2, 8, taps).permute(2, 6, 0, 3, 4, 1, 5)
-            self._bf16[key] = pack.contiguous().to(torch.float16).to(self.w.device)
-        return self._bf16[key]
-
-    def wino_h2_pack(self, tile):
-        """(tile+2)^2 H2 packs of U[p][dz] = (G g G^T)[xi][eta][dz] (taps = 3, or 1 for a 3x3x1 layer), split from the fp64 products."""
-        key = ("h2", tile)
-        if key not in self._wino:
-            G = self._wino_G(tile)
-            n2 = G.shape[0] ** 2
-            kz = self.wino_kz
-            w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, kz)
-            U = torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(n2, self.Cout, self.Cin, kz)
-            npad = -(-self.Cout // 128) * 128
-            Up = torch.zeros(n2, npad, self.Cin, kz, dtype=torch.float64)
-            Up[:, :self.Cout] = U
-            self._wino[key] = torch.stack([self._h2_layout(Up[p]) for p in range(n2)], 0).to(self.w.device)
-        return self._wino[key]
+        return self._cached(("h2", ztrim), lambda: self._h2_layout(self._padded(self._taps(ztrim).double())))
 
     @staticmethod
     def _wino_G(tile):
+        """Toom-Cook G of F(tile, 3): points (0, 1, -1, inf) | (0, -1, 2, 1/2, inf) | (0, 1, -1, 1/2, -2, inf), matching Wino<tile + 2>
+        in csrc/winograd.hip."""
         if tile == 2:
             return torch.tensor([[1., 0., 0.], [.5, .5, .5], [.5, -.5, .5], [0., 0., 1.]], dtype=torch.float64)
         if tile == 3:
@@ -427,59 +413,72 @@ class PackedConv:
         return torch.tensor([[1, 0, 0], [1 / 3, 1 / 3, 1 / 3], [-1 / 3, 1 / 3, -1 / 3], [-16 / 15, -8 / 15, -4 / 15],
                              [1 / 15, -2 / 15, 4 / 15], [0, 0, 1]], dtype=torch.float64)
 
+    def _wino_U(self, tile):
+        """U[p][dz] = (G g G^T)[xi][eta][dz] per transform point p = (tile+2)*xi + eta, products in fp64: [(tile+2)^2, Cout, Cin, kz]
+        (kz = 3 z taps, or 1 for a 3x3x1 layer)."""
+        G = self._wino_G(tile)
+        w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, self.wino_kz)       # [n, c, kx, ky, kz]
+        return torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(G.shape[0] ** 2, self.Cout, self.Cin, self.wino_kz)
+
+    def wino_h2_pack(self, tile):
+        """(tile+2)^2 H2 packs of ``_wino_U``, split from the fp64 products."""
+        return self._cached(("wino_h2", tile), lambda: torch.stack(
+            [self._h2_layout(self._padded(u)) for u in self._wino_U(tile)], 0))
+
     def wino_pack(self, tile):
-        """(tile+2)^2 packs (one per transform point p = (tile+2)*xi + eta) of U[p][dz] = (G g G^T)[xi][eta][dz],
-        taps = 3 (z).  G: F(2,3) / F(4,3) Toom-Cook matrices, products in fp64."""
-        if tile not in self._wino:
-            if tile == 2:
-                G = torch.tensor([[1., 0., 0.], [.5, .5, .5], [.5, -.5, .5], [0., 0., 1.]], dtype=torch.float64)
-            elif tile == 3:
-                # Toom-Cook points (0, -1, 2, 1/2, inf), matching Wino<5>
-                G = torch.tensor([[1, 0, 0], [-2 / 9, 2 / 9, -2 / 9], [1 / 9, 2 / 9, 4 / 9], [-8 / 9, -4 / 9, -2 / 9], [0, 0, 1]],
-                                 dtype=torch.float64)
-            else:
-                # Toom-Cook points (0, 1, -1, 1/2, -2, inf), matching Wino<6> in csrc/winograd.hip
-                G = torch.tensor([[1, 0, 0], [1 / 3, 1 / 3, 1 / 3], [-1 / 3, 1 / 3, -1 / 3], [-16 / 15, -8 / 15, -4 / 15],
-                                  [1 / 15, -2 / 15, 4 / 15], [0, 0, 1]], dtype=torch.float64)
-            n2 = G.shape[0] ** 2
-            kz = self.wino_kz
-            w = self._w_raw.double().view(self.Cout, self.Cin, 3, 3, kz)                # [n, c, kx, ky, kz]
-            U = torch.einsum("pa,qb,ncabz->pqncz", G, G, w).reshape(n2, self.Cout, self.Cin, kz).float().contiguous()
-            lib = _lib.load()
-            n = lib.coocc_conv_pack_weights(ctypes.c_void_p(U[0].data_ptr()), self.Cout, self.Cin, kz, 0, None)
-            packed = torch.empty(n2, n, dtype=_F32)
-            for p in range(n2):
-                lib.coocc_conv_pack_weights(ctypes.c_void_p(U[p].data_ptr()), self.Cout, self.Cin, kz, 0,
-                                            ctypes.c_void_p(packed[p].data_ptr()))
-            self._wino[tile] = packed.to(self.w.device)
-        return self._wino[tile]
+        """(tile+2)^2 fp32 packs of ``_wino_U``, one per transform point."""
+        def build():
+            return torch.stack([lib_pack("coocc_conv_pack_weights", u, self.Cout, self.Cin, self.wino_kz, 0)
+                                for u in self._wino_U(tile).float().contiguous()], 0)
+        return self._cached(("wino", tile), build)
 
 
-_ws_cache = {}
-_wino_ws = {}
-_bf16_ws = {}
 # bf16 path: 1 = round the activations to bf16 in memory once per layer and run k_conv_bf16w (operands staged by
 # global_load_lds); 0 = k_conv_bf16 (fp32 operands rounded inside the K loop)
 BF16_PRECONVERT = __import__("os").environ.get("COOCC_BF16_PRECONVERT", "1") != "0"
 ZSHARE = __import__("os").environ.get("COOCC_BF16_ZSHARE", "1") != "0"       # read by the library too (k_conv_bf16z)
 
+# Every per-stream device buffer of the package, keyed (device index, raw stream handle, kind): Winograd V / M, split-K slabs, H2
+# / bf16 operand rows, arrival counters, amax words, pooling / FPS / voxelisation workspaces.  One dict, so that a captured graph
+# can pin everything its stream owns (``stream_scratch``) without knowing who allocated what.
+_stream_bufs = {}
 
-def _bf16_buffer(device, n):
-    key = (device.index, _lib.stream(device).value)
-    t = _bf16_ws.get(key)
+
+def stream_buffer(device, kind, n, dtype=_F32, zero=False):
+    """The buffer ``kind`` of ``device``'s current stream with at least ``n`` elements.  A buffer that is too small is REPLACED by a
+    fresh one (zeros when ``zero``, else uninitialised) -- the old tensor lives on only where someone holds it (a captured graph)."""
+    key = (device.index, _lib.stream(device).value or 0, kind)      # a NULL c_void_p reads back as None: the default stream is 0
+    t = _stream_bufs.get(key)
     if t is None or t.numel() < n:
-        t = torch.empty(n, device=device, dtype=torch.bfloat16)
-        _bf16_ws[key] = t
+        t = _stream_bufs[key] = (torch.zeros if zero else torch.empty)(n, device=device, dtype=dtype)
     return t
+
+
+def stream_scratch(device, stream):
+    """Every per-stream buffer of ``stream`` (``stream_buffer``): a captured hipGraph holds raw pointers into them and must keep
+    them alive (``graph.DenseGraph``)."""
+    h = stream.cuda_stream
+    return [t for (d, s, _), t in _stream_bufs.items() if d == device.index and s == h]
 
 
 def _wino_buffer(device, kind, nfloats):
-    key = (device.index, kind, torch.cuda.current_stream(device).cuda_stream)
-    t = _wino_ws.get(key)
-    if t is None or t.numel() < nfloats:
-        t = torch.zeros(nfloats, device=device, dtype=_F32)     # padded rows stay zero
-        _wino_ws[key] = t
-    return t
+    return stream_buffer(device, kind, nfloats, zero=True)     # padded rows stay zero
+
+
+def scratch(device, kind, nfloats):
+    """Per-stream scratch buffer (uninitialised), grown on demand."""
+    return stream_buffer(device, "s:" + kind, nfloats)
+
+
+def tile_sem(device, n=4096):
+    """Per-stream arrival counters of the in-kernel split-K reduction (coocc_conv_desc.tile_sem): zero on entry, left zero by
+    every launch, so one buffer serves every layer issued on the stream."""
+    return stream_buffer(device, "sem", n, torch.int32, zero=True)
+
+
+def workspace(device, nfloats=64 << 20):
+    """Split-K scratch (256 MB by default), one per stream (samples overlap), reused by every launch on it."""
+    return stream_buffer(device, "ws", nfloats)
 
 
 def _lcm(a, b):
@@ -488,14 +487,17 @@ def _lcm(a, b):
 
 
 def h2_capable(pc):
-    """The split-f16 engine takes this layer's Winograd-domain GEMM (inference packs only: the training path re-packs its
-    weights on the device every step and stays on the fp32-MFMA kernels)."""
-    return CONV_ENGINE == "h2" and pc.Cin % 32 == 0 and hasattr(pc, "wino_h2_pack")
+    """The split-f16 engine takes this layer's Winograd-domain GEMM (``pc.h2``: it carries the H2 packs)."""
+    return CONV_ENGINE == "h2" and pc.Cin % 32 == 0 and pc.h2
 
 
 def wino_plan(x, pc, M, res_mode):
     """None, or (tile, points, Tx, Ty, rows, G, tile_hint) for the Winograd path of this layer."""
     return _wino_plan_geom(x.B, x.X, x.Y, x.Z, pc, M, res_mode)
+
+
+def wino_eligible(x, pc, M, res_mode):
+    return wino_plan(x, pc, M, res_mode) is not None
 
 
 def _wino_plan_geom(B, X, Y, Z, pc, M, res_mode):
@@ -518,44 +520,6 @@ def _wino_plan_geom(B, X, Y, Z, pc, M, res_mode):
     if pts * G >= 1 << 31:
         return None     # row indices are 32-bit
     return tile, pts, Tx, Ty, rows, G, hint
-
-
-def wino_eligible(x, pc, M, res_mode):
-    return wino_plan(x, pc, M, res_mode) is not None
-
-
-def scratch(device, kind, nfloats):
-    """Per-stream scratch buffer (uninitialised), grown on demand."""
-    key = (device.index, "s:" + kind, torch.cuda.current_stream(device).cuda_stream)
-    t = _wino_ws.get(key)
-    if t is None or t.numel() < nfloats:
-        t = torch.empty(nfloats, device=device, dtype=_F32)
-        _wino_ws[key] = t
-    return t
-
-
-_sem_ws = {}
-
-
-def tile_sem(device, n=4096):
-    """Per-stream arrival counters of the in-kernel split-K reduction (coocc_conv_desc.tile_sem): zero on entry, left zero by
-    every launch, so one buffer serves every layer issued on the stream."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    t = _sem_ws.get(key)
-    if t is None:
-        t = _sem_ws[key] = torch.zeros(n, device=device, dtype=torch.int32)
-    return t
-
-
-def stream_scratch(device, stream):
-    """Every per-stream scratch tensor of ``stream`` (Winograd V / M, split-K slabs, H2 inputs, arrival counters): a captured
-    hipGraph holds raw pointers into them and must keep them alive (``graph.DenseGraph``)."""
-    h = stream.cuda_stream
-    out = [t for k, t in _wino_ws.items() if k[0] == device.index and k[-1] == h]
-    out += [t for k, t in _ws_cache.items() if k[0] == device.index and k[-1] == h]
-    out += [t for k, t in _bf16_ws.items() if k[0] == device.index and k[-1] == h]
-    out += [t for k, t in _sem_ws.items() if k[0] == device.index and k[-1] == h]
-    return out
 
 
 def h2_rows(x):
@@ -587,32 +551,32 @@ def check_h2_overflow(reset=True):
             "(INTEGRATION.md, 'Operand range of the split-f16 engine')." % (32768.0 / (100 * H2_WINO_SCALE[4])))
 
 
-def ztrim_range(Zin, Zout, stride, pad):
-    """First / last z tap of a 3-tap axis that reads a real voxel for at least one output z; on thin grids (Z = 1, 2) the
-    taps outside lo..hi only multiply padding."""
+def ztrim(Zin, Zout, stride, pad):
+    """The z trim of a cubic 3x3x3 layer on a grid with Zin input / Zout output planes: ((lo, hi), the descriptor's
+    (kx, ky, kz, px, py, pz)) when only the z taps lo..hi read a real voxel for at least one output z -- on thin grids
+    (Z = 1, 2) the others only multiply padding, so dropping them is exact.  (None, None) when all three are needed."""
     ok = [kz for kz in range(3) if any(0 <= zo * stride - pad + kz < Zin for zo in range(Zout))]
-    return ok[0], ok[-1]
+    lo, hi = ok[0], ok[-1]
+    return (None, None) if hi - lo == 2 else ((lo, hi), (3, 3, hi - lo + 1, pad, pad, pad - lo))
 
 
 def _route(B, X, Y, Z, pc, rm, splitk):
-    """``route`` -> (family, Winograd plan or None, z trim (lo, hi) or None, taps after the trim)."""
+    """``route`` -> (family, Winograd plan or None, z trim (lo, hi) and its descriptor kernel / padding (``ztrim``) or None, None,
+    taps after the trim)."""
     Xo, Yo, Zo = out_dims(X, Y, Z, pc)
     M = B * Xo * Yo * Zo
     bf16, f16 = CONV_DTYPE == "bf16", CONV_DTYPE == "f16"
     plan = None if (bf16 or f16) else _wino_plan_geom(B, X, Y, Z, pc, M, rm)
     if plan is not None:
-        return "wino", plan, None, pc.wino_kz
-    taps, trim = pc.taps, None
-    if ZTRIM and pc._w_cube is not None:
-        lo, hi = ztrim_range(Z, Zo, pc.stride, pc.pad)
-        if hi - lo < 2:
-            taps, trim = 9 * (hi - lo + 1), (lo, hi)
+        return "wino", plan, None, None, pc.wino_kz
+    trim, kdims = ztrim(Z, Zo, pc.stride, pc.pad) if (ZTRIM and pc._w_cube is not None) else (None, None)
+    taps = pc.taps if trim is None else 9 * kdims[2]
     if f16 and pc.Cin % 64 == 0 and pc._w_taps is not None and rm in (0, 1) and splitk in (0, 1):
-        return "f16", None, trim, taps
+        return "f16", None, trim, kdims, taps
     if (not bf16 and not f16 and CONV_ENGINE == "h2" and H2_DIRECT and pc.Cin % 32 == 0 and pc._w_taps is not None
             and rm in (0, 1) and 2.0 * M * pc.Cin * pc.Cout * taps >= H2_DIRECT_MIN_FLOPS):
-        return "h2", None, trim, taps
-    return "other", None, trim, taps
+        return "h2", None, trim, kdims, taps
+    return "other", None, trim, kdims, taps
 
 
 def route(B, X, Y, Z, pc, rm=0, splitk=0):
@@ -682,14 +646,6 @@ def conv_rows_wino(x, pc, out, relu, res, plan, in_ranges=None, twin=False):
     return out
 
 
-def workspace(device, nfloats=64 << 20):
-    """Split-K scratch (256 MB by default), one per device, reused by every launch on the stream."""
-    key = (device.index, nfloats, _lib.stream(device).value)   # one per stream: samples overlap
-    if key not in _ws_cache:
-        _ws_cache[key] = torch.empty(nfloats, device=device, dtype=_F32)
-    return _ws_cache[key]
-
-
 def conv_desc(device, **fields):
     """A ConvDesc (include/coocc_hip.h coocc_conv_desc) holding ``fields`` and the split-K workspace of ``device``'s stream;
     every other field is zero / NULL."""
@@ -728,7 +684,7 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
         out.h2 = out.h16 = None        # a caller-provided buffer is overwritten: whatever twins it carried are stale
     assert x.C == pc.Cin, "channel mismatch: %d vs %d" % (x.C, pc.Cin)
     rm = res_mode or (1 if res is not None else 0)
-    family, plan, trim, taps = _route(x.B, x.X, x.Y, x.Z, pc, rm, splitk)
+    family, plan, trim, kdims, taps = _route(x.B, x.X, x.Y, x.Z, pc, rm, splitk)
     twin = wants_h2_twin(out, twin_for)
     if family == "wino":
         return conv_rows_wino(x, pc, out, relu, res, plan, twin=twin)
@@ -738,8 +694,7 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
                   B=x.B, Xi=x.X, Yi=x.Y, Zi=x.Z, Xo=Xo, Yo=Yo, Zo=Zo, ksize=pc.ksize, stride=pc.stride, pad=pc.pad,
                   relu=int(relu), res_mode=rm, splitk=splitk, tile_hint=TILE_HINT)
     if trim is not None:
-        # z taps lo..hi only: the others read nothing but padding on this grid
-        d.kx, d.ky, d.kz, d.px, d.py, d.pz = 3, 3, trim[1] - trim[0] + 1, pc.pad, pc.pad, pc.pad - trim[0]
+        d.kx, d.ky, d.kz, d.px, d.py, d.pz = kdims      # z taps lo..hi only: the others read nothing but padding on this grid
     if pc.aniso:
         (d.kx, d.ky, d.kz), (d.px, d.py, d.pz), (d.sx, d.sy, d.sz) = pc.kernel, pc.pads, pc.strides
     same = pc.is_unit_stride and (Xo, Yo, Zo) == (x.X, x.Y, x.Z)
@@ -783,7 +738,7 @@ def conv_rows(x, pc, relu=True, res=None, res_mode=0, out=None, splitk=0, twin_f
     if bf16 and BF16_PRECONVERT and pc.Cin % 64 == 0 and pc._w_taps is not None and taps > 1:    # 1x1x1: HBM-bound either way
         # operands bf16 in memory (k_conv_bf16w): the activations are rounded once per layer into a scratch buffer, the
         # weights once per pack; stride-1 "same" layers share the tile between z taps (k_conv_bf16z)
-        xb = _bf16_buffer(dev, x.B * x.V * pc.Cin)
+        xb = stream_buffer(dev, "bf16", x.B * x.V * pc.Cin, torch.bfloat16)
         call("coocc_rows_to_bf16", x.data(), x.stride, x.B * x.V, pc.Cin, ptr(xb))
         d.in_, d.in_stride, d.w, d.mfma_dtype = ptr(xb), pc.Cin, ptr(pc.bf16_pack(trim)), 2
         name = "k_conv_bf16z" if (same and ZSHARE) else "k_conv_bf16w"

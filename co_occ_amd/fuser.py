@@ -18,10 +18,7 @@ from .registry import FUSION_LAYERS
 _I32, _F32, _I64 = torch.int32, torch.float32, torch.int64
 
 
-_fps_ws = {}
 _side = {}
-
-
 
 
 def _side_stream(dev, cur, which=0):
@@ -66,11 +63,7 @@ def _fps_voxels(q_lin, grid, fps_num, which=0, home=None):
 def _fps_voxels_on_current(q_lin, grid, fps_num):
     dev = q_lin.device
     X, Y, Z = grid
-    need = int(_lib.load().coocc_fps_voxels_ws(X, Y, Z))
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _fps_ws or _fps_ws[key].numel() < need:
-        _fps_ws[key] = torch.empty(need, device=dev, dtype=torch.uint8)
-    ws = _fps_ws[key]
+    ws = _core_mod.stream_buffer(dev, "fps", int(_lib.load().coocc_fps_voxels_ws(X, Y, Z)), torch.uint8)
     out = torch.empty(1, fps_num, device=dev, dtype=_I32)
     call("coocc_fps_voxels", ptr(q_lin), q_lin.numel(), X, Y, Z, fps_num, ptr(out), ptr(ws), ws.numel())
     return out

@@ -63,7 +63,7 @@ class DenseGraph:
             self.out = self._run()
         # The captured launches hold RAW pointers into the stream's scratch buffers (Winograd V / M, split-K slabs, arrival
         # counters): keep those tensors alive for as long as the graph exists.  A later eager call on the same stream that
-        # needs a larger buffer REPLACES the dict entry (core.scratch / _wino_buffer) -- without this reference the old tensor
+        # needs a larger buffer REPLACES the registry's entry (core.stream_buffer) -- without this reference the old tensor
         # would be freed, handed to someone else by the caching allocator, and every replay would scribble over it.
         dev = self.slot.cat4.device
         self._pinned = core.stream_scratch(dev, self.stream)

@@ -16,7 +16,7 @@ import os
 from . import _lib, core
 from ._lib import call, host_f32, ptr
 from .backbone import build_bn
-from .core import PackCache, PackedConv, Rows, TILE_HINT, fold_bn, workspace
+from .core import PackCache, PackedConv, Rows, TILE_HINT, fold_bn, stream_buffer, workspace
 from .registry import Registry
 
 _F32, _I32 = torch.float32, torch.int32
@@ -37,7 +37,6 @@ class Voxelization(nn.Module):
         self.voxel_size, self.point_cloud_range = list(voxel_size), list(point_cloud_range)
         self.max_num_points = max_num_points
         self.max_voxels = tuple(max_voxels) if isinstance(max_voxels, (tuple, list)) else (max_voxels, max_voxels)
-        self._ws = {}
 
     def forward(self, points):
         if not points.is_cuda:
@@ -50,11 +49,7 @@ class Voxelization(nn.Module):
         coors = torch.empty(mv, 3, device=dev, dtype=_I32)
         num = torch.empty(mv, device=dev, dtype=_I32)
         count = torch.empty(1, device=dev, dtype=_I32)
-        need = int(_lib.load().coocc_voxelize_ws(n))
-        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-        if key not in self._ws or self._ws[key].numel() < need:
-            self._ws[key] = torch.empty(need, device=dev, dtype=torch.uint8)
-        ws = self._ws[key]
+        ws = stream_buffer(dev, "voxelize", int(_lib.load().coocc_voxelize_ws(n)), torch.uint8)
         call("coocc_voxelize_hard", ptr(pts), n, F, host_f32(self.point_cloud_range), host_f32(self.voxel_size),
              self.max_num_points, mv, ptr(voxels), ptr(coors), ptr(num), ptr(count), ptr(ws), ws.numel())
         m = int(count.item())

@@ -6,6 +6,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
+from .core import stream_buffer
 
 _I32, _F32 = torch.int32, torch.float32
 
@@ -76,15 +77,8 @@ def ball_query(min_radius, max_radius, sample_num, xyz, center_xyz):
     return idx
 
 
-_pool_ws = {}
-
-
 def _pool_workspace(device, npts, nvox):
-    need = int(_lib.load().coocc_voxel_pool_ws(npts, nvox))
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    if key not in _pool_ws or _pool_ws[key].numel() < need:
-        _pool_ws[key] = torch.empty(need, device=device, dtype=torch.uint8)
-    return _pool_ws[key]
+    return stream_buffer(device, "pool", int(_lib.load().coocc_voxel_pool_ws(npts, nvox)), torch.uint8)
 
 
 def pool_ws_clean(ws, npts, nvox):
