@@ -176,6 +176,8 @@ SIGNATURES = {
     "coocc_fpn_sum": (I, [P, P, I, I, I, I, I, I, P, I, P, P]),
     "coocc_zyx_to_rows": (I, [P, P, I, I, I, I, I, I, I, P]),
     "coocc_lidarseg_points": (I, [P, L, L, L, L, I, I, I, I, P, L, L, I, I, P, I, I, P, P, I, P, P]),
+    "coocc_render_eval_stats": (L, [P, P, P, P, I, I, I, P, P, Z, P]),
+    "coocc_render_panels": (I, [P, P, P, P, I, I, I, P, P]),
 }
 
 _lib = None

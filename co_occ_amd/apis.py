@@ -78,12 +78,51 @@ def save_nuscenes_lidarseg_submission(output_points, save_path, img_metas):
     return save_file
 
 
+def save_rendered_panels(result_or_maps, out_dir, gt_img=None, prefix="view_"):
+    """The comparison images upstream writes from ``simple_test`` (coocc_ray.py:629-636, ``./img_<v>.png``) and from
+    ``save_rendered_img`` (P/utils/save_rendered_img.py:59-77), without ``cv2.putText``: one ``[rgb | gt | normalised depth]`` uint8
+    panel per view, composed on the device (``coocc_render_panels``) and copied to the host once.
+
+    ``result_or_maps``: ``simple_test``'s result (its ``rgbs`` / ``depths``) or a ``(rgbs, depths)`` pair; ``gt_img`` [N,3,H,W]
+    (``img[0][0]``; a result dict may carry it as ``gt_img``).  Writes ``<out_dir>/<prefix><v>.png`` through cv2 or PIL, whichever
+    imports; with neither, ``.npy`` arrays (and a warning that says so).  Returns (paths, panels uint8 numpy [N,H,3W,3]); the
+    channel order of the files is the arrays' (upstream hands the same RGB-ordered array to ``cv2.imwrite``)."""
+    from . import evaluation as E
+    if isinstance(result_or_maps, dict):
+        rgbs, depths = result_or_maps.get("rgbs"), result_or_maps.get("depths")
+        gt_img = gt_img if gt_img is not None else result_or_maps.get("gt_img")
+    else:
+        rgbs, depths = result_or_maps[:2]
+    if rgbs is None or depths is None or gt_img is None:
+        raise ValueError("save_rendered_panels: rgbs, depths (a rendered result) and gt_img are needed")
+    panels = E.render_eval(rgbs, depths, gt_img, panels=True)["panels"].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    writer, ext = None, ".npy"
+    try:
+        import cv2
+        writer, ext = (lambda f, a: cv2.imwrite(f, a)), ".png"
+    except ImportError:
+        try:
+            from PIL import Image
+            writer, ext = (lambda f, a: Image.fromarray(a).save(f)), ".png"
+        except ImportError:
+            import warnings
+            warnings.warn("save_rendered_panels: neither cv2 nor PIL imports; writing the panels as .npy arrays")
+            writer = lambda f, a: np.save(f, a)
+    paths = []
+    for v in range(panels.shape[0]):
+        paths.append(os.path.join(out_dir, "%s%d%s" % (prefix, v, ext)))
+        writer(paths[-1], panels[v])
+    return paths, panels
+
+
 def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=None):
     """The loop of ``custom_single_gpu_test`` (P/coocc/apis/test.py:43-45: ``result = model(return_loss=False, **data)`` once per
     sample) with ``slots`` samples in flight (``co_occ_amd.serving``): a generator of ``(data, result)`` in sample order, ``result``
     = what ``COOCC_Ray.simple_test`` returns for that sample (same tensors, same metrics, fine outputs trimmed to their exact
     size).  ``data``: the keyword arguments of ``simple_test`` (``img_inputs`` / ``img``, ``points``, ``gt_occ``,
-    ``visible_mask``, ``points_occ``, ``img_metas``, ``precomputed``).
+    ``visible_mask``, ``points_occ``, ``img_metas``, ``gt_depths``, ``precomputed``).  With ``model.render_eval`` the render keys
+    (``psnr``, ``psnr_mean``, ``depth_sq_err``, ``depth_valid``) are computed the same way (``coocc_render_eval_stats``).
 
     Nothing in the loop waits for the sample that was just issued: the encoders upstream of the hot path run eagerly at submit
     time; pooling + index search of the next ``ahead`` samples are prefetched under the dense stages (one captured hipGraph
@@ -128,6 +167,18 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
                     parts.append(lseg[1].reshape(-1))
             if out.get("fine_count") is not None:
                 parts.append(out["fine_count"].reshape(-1).to(torch.int64))
+            reval = None
+            if model.render_eval:
+                # the render stats read the slot's maps: here, before the slot can be reused; the float64 block rides in the
+                # same pinned-host copy, bit for bit (viewed as int64)
+                img = data.get("img_inputs", data.get("img"))
+                gi, gdep = model.render_gt_img(img, data.get("precomputed")), data.get("gt_depths")
+                for g in (gi, gdep):
+                    if torch.is_tensor(g) and g.is_cuda:
+                        g.record_stream(ds)
+                reval = model._render_eval_launch(out, gi, gdep)
+                if reval is not None and not model.metrics_on_device:
+                    parts.append(reval[0].view(torch.int64).reshape(-1))
             host = ev = None
             if parts and not (model.metrics_on_device and gt is not None and len(parts) == 1):
                 dev_buf = torch.cat(parts) if len(parts) > 1 else parts[0]
@@ -136,20 +187,20 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
             from . import streams as cstreams
             ev = cstreams.new_event()           # fires after the pinned-host copy above: a copy command, complete when it does
             ev.record(ds)
-        return (data, t, (out, host, both if gt is not None else None, lseg), ev)
+        return (data, t, (out, host, both if gt is not None else None, lseg, reval), ev)
 
     def finish(item):
         data, t, payload, ev = item
         if t is None:
             return data, payload
-        out, host, both, lseg = payload
+        out, host, both, lseg, reval = payload
         ev.synchronize()
         from . import core
         core.check_h2_overflow()
         out = dict(out)
         gt, vm = data.get("gt_occ"), data.get("visible_mask")
         C = ncls_of(out)
-        nm = nl = 0                               # host buffer: [ metrics (nm) | lidarseg matrix (nl) | fine count ]
+        nm = nl = 0                               # host buffer: [ metrics (nm) | lidarseg matrix (nl) | fine count | render stats ]
         if gt is not None:
             nm = both.numel()
         if lseg is not None and not model.metrics_on_device:
@@ -168,6 +219,11 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
         if lseg is not None:
             hist = lseg[1] if model.metrics_on_device else host[nm:nm + nl].numpy().copy()
             out.update(model._lidarseg_finish(lseg[0], hist, data["points_occ"]))
+        if reval is not None:
+            block = reval[0]
+            if not model.metrics_on_device:
+                block = host[host.numel() - block.numel():].view(torch.float64).numpy().reshape(block.shape).copy()
+            out.update(model._render_eval_finish(block, *reval[1:]))
         return data, out
 
     try:

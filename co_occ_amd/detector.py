@@ -100,7 +100,7 @@ class COOCC_Ray(nn.Module):
                  loss_voxel_sem_scal_weight=1.0, loss_voxel_geo_scal_weight=1.0, loss_voxel_lovasz_weight=1.0,
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
-                 pts_backbone=None, pts_neck=None, external_encoders=False, **kwargs):
+                 pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -129,6 +129,10 @@ class COOCC_Ray(nn.Module):
         self.loss_cfg, self.disable_loss_depth = loss_cfg, disable_loss_depth
         self.use_rendering, self.test_rendering = use_rendering, test_rendering
         self.metrics_on_device = False              # True: SC/SSC histograms stay int64 device tensors (no sync)
+        # opt-in: simple_test also judges its rendered maps (coocc_ray.py:626-637: PSNR against the camera images; the squared
+        # depth error of save_rendered_img.py:39-79 when gt_depths carries a map) on the device.  Upstream runs that branch
+        # unconditionally, prints, and writes ./img_<v>.png; here nothing is printed or written (apis.save_rendered_panels does)
+        self.render_eval = bool(render_eval)
         # eval-mode ``simple_test`` runs its dense stage as ONE captured hipGraph launch (co_occ_amd.serving, one slot, results
         # identical to the eager path); COOCC_SIMPLE_TEST_GRAPH=0 or ``model.graph_simple_test = False`` keeps every launch eager
         self.graph_simple_test = __import__("os").environ.get("COOCC_SIMPLE_TEST_GRAPH", "1") != "0"
@@ -497,23 +501,73 @@ class COOCC_Ray(nn.Module):
             voxel_feats, img_feats, _, _, gemo, _ = self.extract_feat(points, img=img, img_metas=img_metas)
             transform = img[1:] if img is not None else None
             out = self.decode(voxel_feats, gemo, img_feats, transform, fine_size=fine_size)
-        return self.finish_test_result(out, gt_occ, visible_mask, points_occ=points_occ, img_metas=img_metas)
+        return self.finish_test_result(out, gt_occ, visible_mask, points_occ=points_occ, img_metas=img_metas,
+                                       gt_img=self.render_gt_img(img, precomputed), gt_depths=gt_depths)
 
-    def finish_test_result(self, out, gt_occ=None, visible_mask=None, points_occ=None, img_metas=None):
+    @staticmethod
+    def render_gt_img(img, precomputed=None):
+        """The images the rendered maps are compared with: ``img[0][0]`` [N,3,H,W] (coocc_ray.py:627), or ``precomputed['gt_img']``
+        when the image encoder was bypassed."""
+        if img is not None and img[0] is not None:
+            return img[0][0]
+        return (precomputed or {}).get("gt_img")
+
+    def finish_test_result(self, out, gt_occ=None, visible_mask=None, points_occ=None, img_metas=None, gt_img=None, gt_depths=None):
         """The tail of ``simple_test`` (coocc_ray.py:539-560, 629-656) on a decoded sample: the reference's result keys and,
-        with ground truth, the SC / SSC confusion matrices; with ``points_occ``, the lidarseg keys."""
+        with ground truth, the SC / SSC confusion matrices; with ``points_occ``, the lidarseg keys; with ``render_eval`` set, rendered
+        maps and ``gt_img``, the render keys ``psnr`` [N] / ``psnr_mean`` (+ ``depth_sq_err`` / ``depth_valid`` [N] when ``gt_depths``
+        gives a map of the maps' size) -- numpy like the other metrics, device tensors under ``metrics_on_device``."""
         out = dict(out)
         out.update(output_voxels=out["pred_c"], target_voxels=gt_occ)
         lseg = self._lidarseg_launch(out, points_occ, img_metas) if points_occ else None
+        reval = self._render_eval_launch(out, gt_img, gt_depths)
+        if reval is not None:
+            out.update(self._render_eval_finish(reval[0] if self.metrics_on_device else reval[0].cpu().numpy(), *reval[1:]))
         if gt_occ is not None:
             out.update(self._metrics(out, gt_occ, visible_mask))
         if lseg is not None:
             labels, hist = lseg
             out.update(self._lidarseg_finish(labels, hist if self.metrics_on_device else hist.cpu().numpy(), points_occ))
-        if (gt_occ is not None or lseg is not None) and not self.metrics_on_device:
+        if (gt_occ is not None or lseg is not None or reval is not None) and not self.metrics_on_device:
             from . import core
             core.check_h2_overflow()          # the metrics were read back: the whole sample has finished on this stream
         return out
+
+    def _render_gt_depth(self, gt_depths, depths):
+        """The depth ground truth of the rendered maps, if ``gt_depths`` holds one of their size: a tensor, or the dataset's
+        tuple with the map at ``DEPTH_GT_INDEX`` (as ``forward_train`` reads it); leading batch dimensions of 1 are dropped."""
+        g = gt_depths
+        if isinstance(g, (list, tuple)):
+            i = self.DEPTH_GT_INDEX
+            g = g[i] if -len(g) <= i < len(g) else None
+        if not torch.is_tensor(g):
+            return None
+        while g.dim() > depths.dim() and g.shape[0] == 1:
+            g = g[0]
+        return g if g.shape == depths.shape and g.device == depths.device else None
+
+    def _render_eval_launch(self, out, gt_img, gt_depths):
+        """coocc_ray.py:626-637 on the device: the stats block of the sample's rendered maps (``coocc_render_eval_stats``) on the
+        CURRENT stream -> (float64 [N,8], PSNR present, depth error present), or None when ``render_eval`` is off, nothing was
+        rendered or the ground truth is missing.  The depth-only variant has no colour maps: depth keys only.  No synchronisation."""
+        if not self.render_eval or out.get("depths") is None:
+            return None
+        rgbs, depths = out.get("rgbs"), out["depths"]
+        gd = self._render_gt_depth(gt_depths, depths)
+        if rgbs is None:
+            gt_img = None
+            if gd is None:
+                return None
+        elif gt_img is None:
+            return None
+        from .evaluation import render_eval_stats
+        return render_eval_stats(rgbs, depths, gt_img, gd), rgbs is not None, gd is not None
+
+    @staticmethod
+    def _render_eval_finish(block, with_rgb, with_depth):
+        """The render keys of a stats block: the host copy (numpy) or the device tensor (``metrics_on_device``)."""
+        from .evaluation import render_eval_keys
+        return render_eval_keys(block, with_rgb, with_depth, extrema=False)
 
     def _lidarseg_launch(self, out, points_occ, img_metas=None):
         """coocc_ray.py:556-560 on the device: the eval labels of ``forward_lidarseg`` (argmax of the softmax over classes

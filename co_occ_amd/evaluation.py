@@ -8,13 +8,18 @@ over a whole validation set and reads them back once.
 
 The lidarseg metrics (``points_occ``: OccHead.forward_lidarseg, occ_head.py:339-383, and simple_evaluation_semantic,
 coocc_ray.py:693-700) take the same route: ``lidarseg_points`` samples the logits at the points, labels them and builds the
-16x16 ``fast_hist_crop`` matrix in one kernel; ``LidarSegEvaluator`` accumulates it over a dataset."""
+16x16 ``fast_hist_crop`` matrix in one kernel; ``LidarSegEvaluator`` accumulates it over a dataset.
+
+The rendered maps of ``test_rendering`` (coocc_ray.py:626-637, P/utils/save_rendered_img.py) are judged the same way:
+``render_eval`` gives the per-view PSNR, the depth error and the comparison panels from two kernels; ``RenderEvaluator``
+accumulates them over a dataset."""
+import contextlib
 import warnings
 
 import numpy as np
 import torch
 
-from ._lib import call, host_f32, ptr
+from ._lib import call, check, host_f32, load, ptr
 
 NOISE = 255
 
@@ -177,3 +182,132 @@ def lidarseg_metrics(hist):
         warnings.simplefilter("ignore", RuntimeWarning)         # nanmean of all-NaN IoUs (an empty matrix) is NaN
         miou = float(np.nanmean(ious))
     return dict(hist=hist, class_ious=ious, mIoU=miou)
+
+
+# ---------------------------------------------------------------- rendered maps (test_rendering)
+# The tail of COOCC_Ray.simple_test under ``use_rendering and test_rendering`` (coocc_ray.py:626-637): PSNR of every rendered colour
+# map against the camera image (compute_psnr, P/utils/save_rendered_img.py:10-20), the [rgb | gt | depth_] uint8 panels, and the
+# squared depth error of save_rendered_img (:39-79) -- on the device.  Columns of the [N, 8] float64 stats block
+# (include/coocc_hip.h, coocc_render_eval_stats):
+RE_SQ_RGB, RE_DMIN, RE_DMAX, RE_SQ_DEPTH, RE_NVALID, RE_PSNR, RE_PSNR_MEAN = range(7)
+RENDER_EVAL_SLOTS = 8
+
+
+def _check_maps(rgbs, depths, gt_img, gt_depth):
+    for name, t in (("rgbs", rgbs), ("depths", depths), ("gt_img", gt_img), ("gt_depth", gt_depth)):
+        if t is not None and not torch.is_tensor(t):
+            raise TypeError("render_eval: %s is a %s, not a tensor" % (name, type(t).__name__))
+    if depths.dim() != 3:
+        raise ValueError("render_eval: depths %s is not [N, H, W]" % (tuple(depths.shape),))
+    N, H, W = depths.shape
+    if (rgbs is None) != (gt_img is None):
+        raise ValueError("render_eval: rgbs and gt_img come together (both, or neither for the depth-only variant)")
+    if rgbs is not None:
+        if tuple(rgbs.shape) != (N, H, W, 3):
+            raise ValueError("render_eval: rgbs %s does not match depths %s ([N, H, W, 3] expected)"
+                             % (tuple(rgbs.shape), tuple(depths.shape)))
+        if tuple(gt_img.shape) != (N, 3, H, W):
+            raise ValueError("render_eval: gt_img %s does not match the rendered maps %s: the maps are 16 fH x 16 fW and must equal "
+                             "the image size ([N, 3, H, W] = %s expected)" % (tuple(gt_img.shape), tuple(rgbs.shape), (N, 3, H, W)))
+    if gt_depth is not None and tuple(gt_depth.shape) != (N, H, W):
+        raise ValueError("render_eval: gt_depth %s does not match depths %s" % (tuple(gt_depth.shape), tuple(depths.shape)))
+    for name, t in (("rgbs", rgbs), ("depths", depths), ("gt_img", gt_img), ("gt_depth", gt_depth)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("co_occ_amd.evaluation runs on the HIP device only (%s is a %s tensor; there is no CPU fallback)"
+                               % (name, t.device))
+    return N, H, W
+
+
+def _f32c(t):
+    return None if t is None else t.float().contiguous()
+
+
+def render_eval_stats(rgbs, depths, gt_img, gt_depth=None, out=None):
+    """``coocc_render_eval_stats`` on the current stream -> the float64 [N, 8] device block (columns RE_*).  rgbs [N,H,W,3] /
+    depths [N,H,W] (the render block's maps), gt_img [N,3,H,W] (``img[0][0]``), gt_depth [N,H,W] or None; ``rgbs = gt_img = None``:
+    the depth-only variant (no PSNR).  No synchronisation, no host read."""
+    N, H, W = _check_maps(rgbs, depths, gt_img, gt_depth)
+    rgbs, depths, gt_img, gt_depth = _f32c(rgbs), _f32c(depths), _f32c(gt_img), _f32c(gt_depth)
+    if out is None:
+        out = torch.empty(N, RENDER_EVAL_SLOTS, dtype=torch.float64, device=depths.device)
+    need = int(load().coocc_render_eval_stats(None, None, None, None, N, H, W, None, None, 0, None))
+    if need < 0:
+        check(need)
+    ws = torch.empty(need // 8, dtype=torch.float64, device=depths.device)
+    call("coocc_render_eval_stats", ptr(rgbs), ptr(depths), ptr(gt_img), ptr(gt_depth), N, H, W, ptr(out, torch.float64), ptr(ws),
+         need)
+    return out
+
+
+def render_panels(rgbs, depths, gt_img, block):
+    """``coocc_render_panels`` -> uint8 [N, H, 3W, 3] on the device: [rgb | gt | normalised depth] per view (coocc_ray.py:629-633).
+    ``block``: the stats block of the same maps (its depth extrema are read on the device)."""
+    N, H, W = _check_maps(rgbs, depths, gt_img, None)
+    if rgbs is None:
+        raise ValueError("render_panels: the panels need rgbs and gt_img (the depth-only variant has no colour maps)")
+    if block is None or tuple(block.shape) != (N, RENDER_EVAL_SLOTS):
+        raise ValueError("render_panels: the stats block of render_eval_stats ([%d, 8] float64) is required" % N)
+    panels = torch.empty(N, H, 3 * W, 3, dtype=torch.uint8, device=depths.device)
+    call("coocc_render_panels", ptr(_f32c(rgbs)), ptr(_f32c(depths)), ptr(_f32c(gt_img)), ptr(block, torch.float64), N, H, W,
+         ptr(panels))
+    return panels
+
+
+def render_eval_keys(block, with_rgb=True, with_depth=False, extrema=True):
+    """The result keys held by a stats block -- a device tensor (the keys stay device tensors: nothing synchronises) or its
+    host copy as a numpy array."""
+    if torch.is_tensor(block):
+        f32, i64 = (lambda a: a.to(torch.float32)), (lambda a: a.to(torch.int64))
+    else:
+        block = np.asarray(block, dtype=np.float64).reshape(-1, RENDER_EVAL_SLOTS)
+        f32, i64 = (lambda a: a.astype(np.float32)), (lambda a: a.astype(np.int64))
+    res = {}
+    if with_rgb:
+        res.update(psnr=f32(block[:, RE_PSNR]), psnr_mean=f32(block[0, RE_PSNR_MEAN]))
+    if extrema:
+        res.update(depth_min=f32(block[:, RE_DMIN]), depth_max=f32(block[:, RE_DMAX]))
+    if with_depth:
+        res.update(depth_sq_err=block[:, RE_SQ_DEPTH], depth_valid=i64(block[:, RE_NVALID]))
+    return res
+
+
+def render_eval(rgbs, depths, gt_img, gt_depth=None, panels=False, stream=None):
+    """PSNR / depth error / comparison panels of rendered maps on the device (``stream``: a torch stream, default the current one).
+    Returns device tensors: ``psnr`` [N] fp32, ``psnr_mean`` (the scalar upstream prints), ``depth_min`` / ``depth_max`` [N]; with
+    ``gt_depth``: ``depth_sq_err`` [N] fp64 = sum (depth - gt_depth)^2 and ``depth_valid`` [N] int64, over gt_depth > 0; with
+    ``panels=True``: ``panels`` uint8 [N,H,3W,3]; always ``stats``, the raw [N, 8] block."""
+    _check_maps(rgbs, depths, gt_img, gt_depth)
+    if panels and rgbs is None:
+        raise ValueError("render_eval: panels need rgbs and gt_img")
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with ctx:
+        block = render_eval_stats(rgbs, depths, gt_img, gt_depth)
+        res = render_eval_keys(block, rgbs is not None, gt_depth is not None)
+        res["stats"] = block
+        if panels:
+            res["panels"] = render_panels(rgbs, depths, gt_img, block)
+    return res
+
+
+class RenderEvaluator:
+    """Whole-dataset accumulation of the render metrics on the device: ``update`` / ``add`` enqueue a few tiny device operations
+    and never synchronise; ``summary`` reads back once.  Sums: psnr over the views, the view count, the squared depth error and
+    its pixel count."""
+
+    def __init__(self, device="cuda"):
+        self.acc = torch.zeros(4, dtype=torch.float64, device=device)       # sum psnr | views | sum sq_depth | sum n_valid
+
+    def add(self, block, with_rgb=True):
+        """Add a stats block already computed (``render_eval(...)['stats']``; a device tensor or numpy)."""
+        b = torch.as_tensor(np.asarray(block) if not torch.is_tensor(block) else block).reshape(-1, RENDER_EVAL_SLOTS).to(self.acc)
+        n = float(b.shape[0])
+        psnr = b[:, RE_PSNR].sum() if with_rgb else b.new_zeros(())
+        self.acc += torch.stack([psnr, b.new_tensor(n if with_rgb else 0.0), b[:, RE_SQ_DEPTH].sum(), b[:, RE_NVALID].sum()])
+
+    def update(self, rgbs, depths, gt_img, gt_depth=None):
+        self.add(render_eval_stats(rgbs, depths, gt_img, gt_depth), with_rgb=rgbs is not None)
+
+    def summary(self):
+        psnr, views, sq, nv = self.acc.cpu().tolist()
+        return dict(psnr_mean=psnr / views if views else float("nan"), views=int(views), depth_sq_err=sq, depth_valid=int(nv),
+                    depth_mse=sq / nv if nv else float("nan"), depth_rmse=(sq / nv) ** 0.5 if nv else float("nan"))

@@ -773,6 +773,26 @@ int coocc_lidarseg_points(const float* logits, int64_t stride_c, int64_t stride_
                           int label_col, const float* range_host, int padding_mode, int mode, float* probs, int64_t* labels,
                           int accumulate, int64_t* hist, void* stream);
 
+/* Evaluation of the rendered maps: the test_rendering tail of COOCC_Ray.simple_test (P/coocc/detectors/coocc_ray.py:626-637),
+ * compute_psnr (P/utils/save_rendered_img.py:10-20) and the squared depth error of save_rendered_img (:39-79) in one pass over
+ * the maps, without the device->host copy.  rgbs:[N,H,W,3] and depths:[N,H,W] as coocc_upsample_maps writes them; gt_img:[N,3,H,W]
+ * (the reference's img[0][0], not denormalised); gt_depth:[N,H,W] or NULL.  rgbs and gt_img may both be NULL (the depth-only
+ * LiDAR variant: no PSNR).  block:[N,8] doubles (device), per view:
+ *   [0] sum (rgb - gt)^2 over H*W*3   [1] min and [2] max of the depth map   [3] sum (depth - gt_depth)^2 and [4] the pixel count,
+ *   both over gt_depth > 0   [5] psnr = -10 ln([0] / (3HW)) / ln 10 from the fp64 sum, rounded to fp32 (+inf for a zero error;
+ *   NaN without rgbs)   [6] the mean of [5] over the views (sequential fp32 sum / N as upstream, repeated in every row)   [7] 0.
+ * fp64 partials per workgroup in ws, added in a fixed order by the last step: no floating-point atomics, run-to-run bit-equal,
+ * no host read (capturable).  ws == NULL: returns the workspace bytes for (N, H, W) and launches nothing; otherwise 0 or a
+ * negative COOCC_E* code. */
+int64_t coocc_render_eval_stats(const float* rgbs, const float* depths, const float* gt_img, const float* gt_depth, int N, int H,
+                                int W, double* block, void* ws, size_t ws_bytes, void* stream);
+/* The comparison panels of coocc_ray.py:629-633: panels:[N,H,3W,3] u8 = np.uint8(cat([rgb, gt (NCHW -> HWC), depth_ repeated over
+ * 3 channels], dim=1).clip(0, 1) * 255.0) with depth_ = (d - dmin) / ((dmax - dmin) + 1e-8f); fp32 operations in upstream's order,
+ * IEEE division, no contraction: the CPU's bytes.  dmin / dmax are read from `block` (coocc_render_eval_stats's, required) on the
+ * device: no host read between the two launches. */
+int coocc_render_panels(const float* rgbs, const float* depths, const float* gt_img, const double* block, int N, int H, int W,
+                        uint8_t* panels, void* stream);
+
 /* ---------------------------------------------------------------- LiDAR producer */
 /* Hard voxelisation (mmdet3d/ops/voxel/src/voxelization_cpu.cpp:44-104 = the deterministic CUDA path of
  * voxelization_cuda.cu): points:[n,F] (xyz first); range_host:[6] xyzxyz min/max; voxel_size_host:[3].
