@@ -25,6 +25,8 @@ from .calibration import calibrate
 from . import apis, evaluation
 from . import lidar
 from .lidar import HardSimpleVFE, SparseLiDAREnc4x, SparseLiDAREnc8x, Voxelization
+from . import lidar_hd
+from .lidar_hd import SparseEncoderHD
 from .evaluation import SemanticEvaluator, cm_to_ious, evaluation_semantic
 
 register_into_mmdet()

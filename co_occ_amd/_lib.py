@@ -165,6 +165,8 @@ SIGNATURES = {
     "coocc_sparse_index_map": (I, [P, I, I, I, I, P, P]),
     "coocc_sparse_conv_table": (I, [P, I, I, I, I, I, I, I, P, P, P]),
     "coocc_sparse_down_flags": (I, [P, I, I, I, I, I, I, I, P, P]),
+    "coocc_sparse_conv_table3": (I, [P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P]),
+    "coocc_sparse_down_flags3": (I, [P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P]),
     "coocc_sparse_lin_to_coors": (I, [P, I, I, I, I, P, P, P]),
     "coocc_bn_stats": (I, [P, I, I, I, P, P, P, Z, P]),
     "coocc_bn_apply": (I, [P, I, I, P, P, P, P, F, P, I, P, P]),

@@ -152,11 +152,13 @@ extern "C" int coocc_vfe_mean(const float* voxels, const int32_t* num_points, in
 
 // ------------------------------------------------------------------ sparse rule books (dense index map per resolution)
 // coors: [M,3] (z, y, x) int32 (batch 1); dims = (D, H, W) = spatial shape in (z, y, x) order.
-__global__ __launch_bounds__(256) void k_sp_index_map(const int32_t* __restrict__ coors, int M, int H, int W,
+__global__ __launch_bounds__(256) void k_sp_index_map(const int32_t* __restrict__ coors, int M, int D, int H, int W,
                                                        int32_t* __restrict__ map) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= M) return;
-  map[((size_t)coors[i * 3] * H + coors[i * 3 + 1]) * W + coors[i * 3 + 2]] = i;
+  const int z = coors[i * 3], y = coors[i * 3 + 1], x = coors[i * 3 + 2];
+  if ((unsigned)z >= (unsigned)D || (unsigned)y >= (unsigned)H || (unsigned)x >= (unsigned)W) return;   // not a voxel of this grid: no write
+  map[((size_t)z * H + y) * W + x] = i;
 }
 
 extern "C" int coocc_sparse_index_map(const int32_t* coors, int M, int D, int H, int W, int32_t* map, void* stream) {
@@ -164,7 +166,7 @@ extern "C" int coocc_sparse_index_map(const int32_t* coors, int M, int D, int H,
   hipStream_t s = as_stream(stream);
   COOCC_HIP(hipMemsetAsync(map, 0xFF, sizeof(int32_t) * (size_t)D * H * W, s));
   if (M == 0) return COOCC_OK;
-  hipLaunchKernelGGL(k_sp_index_map, dim3(cdiv(M, 256)), dim3(256), 0, s, coors, M, H, W, map);
+  hipLaunchKernelGGL(k_sp_index_map, dim3(cdiv(M, 256)), dim3(256), 0, s, coors, M, D, H, W, map);
   COOCC_LAUNCH_CHECK("k_sp_index_map");
   return COOCC_OK;
 }
@@ -240,5 +242,95 @@ extern "C" int coocc_sparse_lin_to_coors(const int32_t* lin, int n, int D, int H
   if (n == 0) return COOCC_OK;
   hipLaunchKernelGGL(k_sp_lin_to_coors, dim3(cdiv(n, 256), D), dim3(256), 0, as_stream(stream), lin, n, H, W, coors, dense_rows);
   COOCC_LAUNCH_CHECK("k_sp_lin_to_coors");
+  return COOCC_OK;
+}
+
+// ------------------------------------------------------------------ rule books with per-axis geometry (SparseEncoderHD)
+// mmdet3d/ops/spconv (v1): kernel (kz,ky,kx), stride (sz,sy,sx), padding (pz,py,px), e.g. the third down-convolution of
+// projects/configs/coocc_nusc/coocc_lidar.py with padding [0,1,1].  Tap order stays spconv's: t = (kd*ky + kh)*kx + kw;
+// input position = o*s - p + tap per axis.  Cases the cubic pad-1 path never met: an active input that reaches NO output (pad 0
+// on an even extent: every candidate output lies past the last one), taps outside on one axis only, extents that differ
+// per axis.  Thread indices and the [taps][Mo] table offsets are 64-bit; linear CELL ids stay int32 (coocc_compact_flags and
+// coocc_sparse_lin_to_coors carry them as int32), which the argument checks enforce.
+struct Zyx { int z, y, x; };
+
+static bool sp3_geometry_ok(Zyx k, Zyx s, Zyx p) {
+  return k.z > 0 && k.y > 0 && k.x > 0 && k.z <= 7 && k.y <= 7 && k.x <= 7 && s.z > 0 && s.y > 0 && s.x > 0 && s.z <= 64 && s.y <= 64 &&
+         s.x <= 64 && p.z >= 0 && p.y >= 0 && p.x >= 0 && p.z <= 64 && p.y <= 64 && p.x <= 64;
+}
+static bool sp3_cells_fit_i32(int D, int H, int W) {
+  return D > 0 && H > 0 && W > 0 && (long long)D * H * W <= 0x7FFFFFFFll;
+}
+
+__global__ __launch_bounds__(256) void k_sp_table3(const int32_t* __restrict__ out_coors, int Mo, int Di, int Hi, int Wi, Zyx k, Zyx s,
+                                                    Zyx p, const int32_t* __restrict__ in_map, int32_t* __restrict__ table) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int taps = k.z * k.y * k.x;
+  if (i >= (long long)Mo * taps) return;
+  const int t = (int)(i / Mo);
+  const size_t o = (size_t)(i % Mo);
+  const int kw = t % k.x, kh = (t / k.x) % k.y, kd = t / (k.x * k.y);
+  const int z = out_coors[o * 3] * s.z - p.z + kd, y = out_coors[o * 3 + 1] * s.y - p.y + kh, x = out_coors[o * 3 + 2] * s.x - p.x + kw;
+  int r = -1;
+  if ((unsigned)z < (unsigned)Di && (unsigned)y < (unsigned)Hi && (unsigned)x < (unsigned)Wi) r = in_map[((size_t)z * Hi + y) * Wi + x];
+  table[i] = r;
+}
+
+extern "C" int coocc_sparse_conv_table3(const int32_t* out_coors, int Mo, int Di, int Hi, int Wi, int kz, int ky, int kx, int sz, int sy,
+                                        int sx, int pz, int py, int px, const int32_t* in_map, int32_t* table, void* stream) {
+  const Zyx k{kz, ky, kx}, s{sz, sy, sx}, p{pz, py, px};
+  COOCC_CHECK_ARG(Mo >= 0 && in_map && ((out_coors && table) || Mo == 0), "sparse_conv_table3: bad args (null pointer or negative row count)");
+  COOCC_CHECK_ARG(sp3_geometry_ok(k, s, p), "sparse_conv_table3: kernel (%d,%d,%d) / stride (%d,%d,%d) / padding (%d,%d,%d): extents 1..7, "
+                  "strides 1..64, paddings 0..64 per axis", kz, ky, kx, sz, sy, sx, pz, py, px);
+  COOCC_CHECK_ARG(sp3_cells_fit_i32(Di, Hi, Wi), "sparse_conv_table3: input grid %d x %d x %d: extents must be positive and the grid "
+                  "at most 2^31 - 1 cells (linear cell ids are int32)", Di, Hi, Wi);
+  const long long n = (long long)Mo * kz * ky * kx;           // 64-bit: Mo * taps passes 2^31 from 6.3 M rows at 343 taps
+  COOCC_CHECK_ARG((n + 255) / 256 <= 0x7FFFFFFFll, "sparse_conv_table3: %lld table entries exceed one launch (2^31 - 1 blocks of 256)", n);
+  if (Mo == 0) return COOCC_OK;
+  hipLaunchKernelGGL(k_sp_table3, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), out_coors, Mo, Di, Hi, Wi, k, s, p, in_map,
+                     table);
+  COOCC_LAUNCH_CHECK("k_sp_table3");
+  return COOCC_OK;
+}
+
+// SparseConv3d active-output flags: every output o with o*s - p + tap = i on all three axes, 0 <= o < (Do, Ho, Wo), of an
+// active input i (geometry.h:25-86 getValidOutPos).  An input none of whose taps lands on such an o sets nothing.
+__global__ __launch_bounds__(256) void k_sp_down_flags3(const int32_t* __restrict__ coors, int M, int Di, int Hi, int Wi, Zyx k, Zyx s,
+                                                         Zyx p, int Do, int Ho, int Wo, uint8_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int taps = k.z * k.y * k.x;
+  if (i >= (long long)M * taps) return;
+  const size_t m = (size_t)(i / taps);
+  const int t = (int)(i % taps);
+  const int kw = t % k.x, kh = (t / k.x) % k.y, kd = t / (k.x * k.y);
+  const int cz = coors[m * 3], cy = coors[m * 3 + 1], cx = coors[m * 3 + 2];
+  if ((unsigned)cz >= (unsigned)Di || (unsigned)cy >= (unsigned)Hi || (unsigned)cx >= (unsigned)Wi) return;   // not a voxel of this grid
+  const int z = cz + p.z - kd, y = cy + p.y - kh, x = cx + p.x - kw;
+  if (z < 0 || y < 0 || x < 0 || z % s.z || y % s.y || x % s.x) return;
+  const int oz = z / s.z, oy = y / s.y, ox = x / s.x;
+  if (oz < Do && oy < Ho && ox < Wo) flags[((size_t)oz * Ho + oy) * Wo + ox] = 1;
+}
+
+extern "C" int coocc_sparse_down_flags3(const int32_t* coors, int M, int Di, int Hi, int Wi, int kz, int ky, int kx, int sz, int sy, int sx,
+                                        int pz, int py, int px, int Do, int Ho, int Wo, uint8_t* flags, void* stream) {
+  const Zyx k{kz, ky, kx}, s{sz, sy, sx}, p{pz, py, px};
+  COOCC_CHECK_ARG((coors || M == 0) && flags && M >= 0, "sparse_down_flags3: bad args (null pointer or negative row count)");
+  COOCC_CHECK_ARG(sp3_geometry_ok(k, s, p), "sparse_down_flags3: kernel (%d,%d,%d) / stride (%d,%d,%d) / padding (%d,%d,%d): extents 1..7, "
+                  "strides 1..64, paddings 0..64 per axis", kz, ky, kx, sz, sy, sx, pz, py, px);
+  COOCC_CHECK_ARG(sp3_cells_fit_i32(Di, Hi, Wi), "sparse_down_flags3: input grid %d x %d x %d: extents must be positive and the grid "
+                  "at most 2^31 - 1 cells (linear cell ids are int32)", Di, Hi, Wi);
+  // ops.py get_conv_output_size per axis; the flag volume is written with these extents, so they are checked, not trusted
+  COOCC_CHECK_ARG(Di + 2 * pz >= kz && Hi + 2 * py >= ky && Wi + 2 * px >= kx && Do == (Di + 2 * pz - kz) / sz + 1 &&
+                      Ho == (Hi + 2 * py - ky) / sy + 1 && Wo == (Wi + 2 * px - kx) / sx + 1,
+                  "sparse_down_flags3: output grid %d x %d x %d is not (in + 2 p - k) / s + 1 per axis of %d x %d x %d", Do, Ho, Wo, Di, Hi,
+                  Wi);
+  COOCC_CHECK_ARG(sp3_cells_fit_i32(Do, Ho, Wo), "sparse_down_flags3: output grid %d x %d x %d exceeds 2^31 - 1 cells", Do, Ho, Wo);
+  const long long n = (long long)M * kz * ky * kx;
+  COOCC_CHECK_ARG((n + 255) / 256 <= 0x7FFFFFFFll, "sparse_down_flags3: %lld (voxel, tap) pairs exceed one launch (2^31 - 1 blocks of 256)", n);
+  hipStream_t st = as_stream(stream);
+  COOCC_HIP(hipMemsetAsync(flags, 0, (size_t)Do * Ho * Wo, st));
+  if (M == 0) return COOCC_OK;
+  hipLaunchKernelGGL(k_sp_down_flags3, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, coors, M, Di, Hi, Wi, k, s, p, Do, Ho, Wo, flags);
+  COOCC_LAUNCH_CHECK("k_sp_down_flags3");
   return COOCC_OK;
 }

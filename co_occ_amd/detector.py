@@ -89,6 +89,9 @@ def _drop_captured_pipeline(module, incompatible_keys):
 @DETECTORS.register_module()
 class COOCC_Ray(nn.Module):
     WITH_RGB_HEAD = True          # COOCC_Ray_L has the sigma head only (coocc_ray_lidar.py:111-112)
+    # SparseEncoderHD returns the dense [B,C,Z,Y,X] tensor SECOND3D takes; the fusion detector's extract_pts_feat reads the dict
+    # (x, pts_feats) of the 8x / 4x encoders (coocc_ray.py:215-234), upstream as here: only COOCC_Ray_L can run it
+    TAKES_SPARSE_ENCODER_HD = False
 
     def __init__(self, voxel_size=None, n_voxels=None, loss_cfg=None, aabb=None, near_far_range=None,
                  N_samples=40, N_rand=4096, depth_supervise=False, use_nerf_mask=True, nerf_sample_view=3,
@@ -100,7 +103,8 @@ class COOCC_Ray(nn.Module):
                  loss_voxel_sem_scal_weight=1.0, loss_voxel_geo_scal_weight=1.0, loss_voxel_lovasz_weight=1.0,
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
-                 pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, **kwargs):
+                 pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
+                 **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -109,8 +113,18 @@ class COOCC_Ray(nn.Module):
         self.pts_voxel_layer = lidar.Voxelization(**pts_voxel_layer) if pts_voxel_layer else None
         self.pts_voxel_encoder = lidar.VOXEL_ENCODERS.build(pts_voxel_encoder) if pts_voxel_encoder else None
         self.pts_middle_encoder = None
+        # opt-in: a ``pts_middle_encoder`` of type SparseEncoderHD (coocc_lidar.py) is built from ``lidar_hd`` -- the HIP sparse
+        # engine -- instead of staying upstream (spconv v1, which does not build on ROCm)
+        self.sparse_encoder_hd = bool(sparse_encoder_hd)
         if pts_middle_encoder:
-            if pts_middle_encoder.get("type") in lidar.MIDDLE_ENCODERS:
+            if self.sparse_encoder_hd and pts_middle_encoder.get("type") == "SparseEncoderHD":
+                if not self.TAKES_SPARSE_ENCODER_HD:
+                    raise NotImplementedError("%s: sparse_encoder_hd=True with pts_middle_encoder type 'SparseEncoderHD' -- that encoder "
+                                              "returns the dense [B,C,Z,Y,X] volume of the LiDAR-only trunk, which this detector's "
+                                              "extract_pts_feat does not take (upstream's neither); use COOCC_Ray_L" % type(self).__name__)
+                from . import lidar_hd
+                self.pts_middle_encoder = lidar_hd.MIDDLE_ENCODERS_HD.build(pts_middle_encoder)
+            elif pts_middle_encoder.get("type") in lidar.MIDDLE_ENCODERS:
                 # trains like upstream (sparse_lidar_enc.py:125-176; batch-statistics BN1d, gradients through the rule books:
                 # co_occ_amd/lidar.py ``SparseConvFn``); ``freeze_lidar_encoder()`` restores the round-2..4 behaviour
                 self.pts_middle_encoder = lidar.MIDDLE_ENCODERS.build(pts_middle_encoder)
@@ -663,11 +677,13 @@ class COOCC_Ray_L(COOCC_Ray):
     """LiDAR-only variant (P/coocc/detectors/coocc_ray_lidar.py): same decoder and depth-only render regulariser (no
     rgb head, :111-112; depth ground truth at gt_depths[-2], :507).  Its dense trunk ``pts_backbone`` / ``pts_neck`` (SECOND3D /
     SECOND3DFPN, projects/configs/coocc_nusc/coocc_lidar.py) is built from the unchanged config through this package's
-    registries and runs on the HIP engine (``lidar_trunk``).  The ``SparseEncoderHD`` middle encoder in front of it (spconv) stays
-    upstream and is resolved like the image encoder of COOCC_Ray (mmdet3d registries, injected modules, or
+    registries and runs on the HIP engine (``lidar_trunk``).  The ``SparseEncoderHD`` middle encoder in front of it is built from
+    ``lidar_hd`` (the HIP sparse engine) under ``sparse_encoder_hd=True`` -- the model then runs from a raw point cloud: eager
+    voxelise -> VFE -> encoder -> trunk, then the decoder; by default it is left to the caller as before (an injected module, or
     ``external_encoders``); ``precomputed=dict(pts_middle_feats=...)`` (its dense [B,C,Z,Y,X] output) runs the trunk without it."""
     WITH_RGB_HEAD = False
     DEPTH_GT_INDEX = -2
+    TAKES_SPARSE_ENCODER_HD = True
 
     def trunk_from_middle(self, x):
         """SparseEncoderHD's dense output [B,C,Z,Y,X] (a tensor, Rows, or a view that remembers them) -> (pts_voxel_feats
@@ -707,6 +723,9 @@ class COOCC_Ray_L(COOCC_Ray):
         return precomputed
 
     def serving_frame(self, img=None, points=None, img_metas=None, precomputed=None):
+        if precomputed is None and img is None and points is not None:
+            # LiDAR-only from the cloud (no image branch to run): the LiDAR producer eagerly, as the base class does for a full frame
+            precomputed = dict(pts_voxel_feats=self.extract_pts_feat(points)[0])
         return super().serving_frame(img, points, img_metas, self._with_trunk(precomputed))
 
     def forward_train(self, points=None, img_metas=None, img_inputs=None, gt_occ=None, points_occ=None, visible_mask=None,

@@ -73,14 +73,15 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
     return DETECTORS.build(dict(cfg, **overrides))
 
 
-def register_into_mmdet(detectors=False):
+def register_into_mmdet(detectors=False, sparse_encoder_hd=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
     the LiDAR producer) -- the reference's own ``COOCC_Ray`` then builds them from its unchanged configs and keeps its
     encoders, losses and metrics.  ``detectors=True`` additionally replaces ``COOCC_Ray`` / ``COOCC_Ray_L`` with ours (HIP
-    render block, on-device metrics; its image encoder is built back through these same registries).  Returns False when
-    mmdet / mmdet3d are not importable."""
+    render block, on-device metrics; its image encoder is built back through these same registries).
+    ``sparse_encoder_hd=True`` additionally replaces mmdet3d's ``SparseEncoderHD`` middle encoder (spconv v1) with
+    ``lidar_hd.SparseEncoderHD``.  Returns False when mmdet / mmdet3d are not importable."""
     try:
         from mmdet.models import builder as mb
         from mmdet3d.models import builder as m3b
@@ -91,6 +92,9 @@ def register_into_mmdet(detectors=False):
         pairs.append((DETECTORS, mb.DETECTORS))
     from . import lidar
     pairs += [(lidar.VOXEL_ENCODERS, m3b.VOXEL_ENCODERS), (lidar.MIDDLE_ENCODERS, m3b.MIDDLE_ENCODERS)]
+    if sparse_encoder_hd:
+        from . import lidar_hd
+        pairs.append((lidar_hd.MIDDLE_ENCODERS_HD, m3b.MIDDLE_ENCODERS))
     for ours, theirs in pairs:
         for k, cls in ours.module_dict.items():
             theirs.register_module(name=k, force=True, module=cls)

@@ -815,6 +815,14 @@ int coocc_sparse_conv_table(const int32_t* out_coors, int Mo, int Di, int Hi, in
                             const int32_t* in_map, int32_t* table /*[k^3][Mo]*/, void* stream);
 int coocc_sparse_down_flags(const int32_t* coors, int M, int ksize, int stride, int pad, int Do, int Ho, int Wo,
                             uint8_t* flags /*[Do*Ho*Wo]*/, void* stream);
+/* Per-axis forms (mmdet3d/ops/spconv v1, SparseEncoderHD): kernel (kz,ky,kx), stride (sz,sy,sx), padding (pz,py,px); tap
+ * t = (kd*ky + kh)*kx + kw; table:[kz*ky*kx][Mo].  coocc_sparse_down_flags3 checks (Do,Ho,Wo) = (in + 2p - k)/s + 1 per axis; an
+ * active input that reaches no output sets no flag.  Offsets into the table are 64-bit; a GRID of more than 2^31 - 1 cells is
+ * refused (linear cell ids are int32 in coocc_compact_flags / coocc_sparse_lin_to_coors). */
+int coocc_sparse_conv_table3(const int32_t* out_coors, int Mo, int Di, int Hi, int Wi, int kz, int ky, int kx, int sz, int sy,
+                             int sx, int pz, int py, int px, const int32_t* in_map, int32_t* table, void* stream);
+int coocc_sparse_down_flags3(const int32_t* coors, int M, int Di, int Hi, int Wi, int kz, int ky, int kx, int sz, int sy, int sx,
+                             int pz, int py, int px, int Do, int Ho, int Wo, uint8_t* flags, void* stream);
 /* linear ids (z*H + y)*W + x -> coors:[n,3] and (optionally) the channels-last rows (x*H + y)*D + z of the dense volume */
 int coocc_sparse_lin_to_coors(const int32_t* lin, int n, int D, int H, int W, int32_t* coors, int32_t* dense_rows,
                               void* stream);
