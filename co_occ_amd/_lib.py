@@ -177,6 +177,8 @@ SIGNATURES = {
     "coocc_eval_semantic": (I, [P, L, L, L, L, I, I, I, I, P, P, I, I, I, I, I, P, P]),
     "coocc_fpn_sum": (I, [P, P, I, I, I, I, I, I, P, I, P, P]),
     "coocc_zyx_to_rows": (I, [P, P, I, I, I, I, I, I, I, P]),
+    "coocc_conv_tap_table3": (I, [I] * 17 + [P, P]),
+    "coocc_fpn_sum_bwd": (I, [P, I, P, P, I, I, I, I, I, I, P]),
     "coocc_lidarseg_points": (I, [P, L, L, L, L, I, I, I, I, P, L, L, I, I, P, I, I, P, P, I, P, P]),
     "coocc_render_eval_stats": (L, [P, P, P, P, I, I, I, P, P, Z, P]),
     "coocc_render_panels": (I, [P, P, P, P, I, I, I, P, P]),

@@ -1017,3 +1017,326 @@ def conv3d_bn_train_rows(x2d, weight, geom, bn, stride=1, pad=None, relu=True, r
     BatchNormRowsFn normalises.  Use conv3d_rows(bn=...) for frozen statistics."""
     y, g = conv3d_rows(x2d, weight, geom, bias=bias, bn=None, stride=stride, pad=pad, relu=False)
     return BatchNormRowsFn.apply(y, bn.weight, bn.bias, res2d, bn, relu, _sync_group(bn, sync)), g
+
+
+# ----------------------------------------------------------------------------- LiDAR-only trunk (SECOND3D + SECOND3DFPN)
+# Training of lidar_trunk's modules.  The anisotropic layers (3x3x1 kernels, strides (s, s, 1), pads (1, 1, 0)) have a Function of
+# their own beside ConvRowsFn -- whose cubic routes stay as they are -- on the same kernels: coocc_conv_fwd through the descriptor's
+# per-axis fields, the same launch with flipped weights for the stride-1 dgrad, row-table launches per residue class for the strided
+# one, coocc_conv_wgrad over the live taps.  Direct form throughout: the one-z-tap Winograd form of inference is not extended to
+# training (the device-side Winograd packs are 3x3x3 only).
+_tables3, _live3, _classes3 = {}, {}, {}
+
+
+def out_dims3(dims, kernel, strides, pads):
+    return tuple(out_dim(n, k, s, p) for n, k, s, p in zip(dims, kernel, strides, pads))
+
+
+def tap_table3(dev, B, Xi, Yi, Zi, kernel, strides, pads, dgrad):
+    """``tap_table`` for per-axis kernel / stride / padding triples (coocc_conv_tap_table3), cached per geometry."""
+    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads, bool(dgrad))
+    if key not in _tables3:
+        Xo, Yo, Zo = out_dims3((Xi, Yi, Zi), kernel, strides, pads)
+        M = B * Xi * Yi * Zi if dgrad else B * Xo * Yo * Zo
+        t = torch.empty(kernel[0] * kernel[1] * kernel[2], M, dtype=torch.int32, device=dev)
+        call("coocc_conv_tap_table3", B, Xi, Yi, Zi, Xo, Yo, Zo, *kernel, *strides, *pads, int(bool(dgrad)), ptr(t))
+        _tables3[key] = t
+    return _tables3[key]
+
+
+def live_taps3(dev, B, Xi, Yi, Zi, kernel, strides, pads):
+    """``live_taps`` of the per-axis forward table."""
+    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads)
+    if key not in _live3:
+        tb = tap_table3(dev, B, Xi, Yi, Zi, kernel, strides, pads, False)
+        idx = torch.nonzero((tb >= 0).any(1)).flatten()
+        _live3[key] = (idx, tb[idx].contiguous())
+    return _live3[key]
+
+
+def dgrad_classes3(dev, B, Xi, Yi, Zi, kernel, strides, pads):
+    """``dgrad_classes`` over the residue classes of (x mod sx, y mod sy, z mod sz).  Stride 4 with a 3-wide kernel: the class
+    x mod 4 == 2 (pad 1) is reached through no tap -- no output reads those voxels -- and is left out; their gradient is the zero
+    the caller initialised."""
+    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads)
+    if key not in _classes3:
+        tb = tap_table3(dev, B, Xi, Yi, Zi, kernel, strides, pads, True)          # [taps, Mi]: output row or -1
+        sx, sy, sz = strides
+        m = torch.arange(B * Xi * Yi * Zi, device=dev)
+        cls = (((m // (Yi * Zi)) % Xi % sx) * sy + (m // Zi) % Yi % sy) * sz + m % Zi % sz
+        out = []
+        for c in range(sx * sy * sz):
+            rows = torch.nonzero(cls == c).flatten()
+            if rows.numel() == 0:
+                continue
+            sub = tb[:, rows]
+            taps = torch.nonzero((sub >= 0).any(1)).flatten()
+            if taps.numel() == 0:
+                continue
+            out.append((rows.int().contiguous(), taps, sub[taps].contiguous()))
+        _classes3[key] = out
+    return _classes3[key]
+
+
+def _conv_launch3(x2d, in_C, w_packed, out2d, Cout, taps, geom_in, geom_out, kernel, strides, pads, scale, shift, relu, table=None,
+                  tag="conv_fwd", out_rows=None, h2_alpha=None, alpha_dev=None):
+    """``_conv_launch`` with the descriptor's per-axis kernel / padding / stride fields."""
+    M = out_rows.shape[0] if out_rows is not None else out2d.shape[0]
+    d = conv_desc(x2d.device, in_=ptr(x2d), w=ptr(w_packed), out=ptr(out2d), scale=ptr(scale), bias=ptr(shift),
+                  gather=ptr(table, torch.int32), out_rows=ptr(out_rows, torch.int32), M=M, Cin=in_C, Cout=Cout, taps=taps,
+                  in_stride=x2d.shape[1], out_stride=out2d.shape[1], B=geom_in[0], Xi=geom_in[1], Yi=geom_in[2], Zi=geom_in[3],
+                  Xo=geom_out[1], Yo=geom_out[2], Zo=geom_out[3], ksize=max(kernel), stride=max(strides), pad=max(pads),
+                  relu=int(relu), tile_hint=TILE_HINT)
+    (d.kx, d.ky, d.kz), (d.px, d.py, d.pz), (d.sx, d.sy, d.sz) = kernel, pads, strides
+    if h2_alpha is not None:
+        d.in_stride, d.mfma_dtype, d.alpha, d.alpha_dev, tag = in_C, 3, float(h2_alpha), alpha_dev, "k_gemm_h2 " + tag
+    launch_conv(d, x2d.device, tag, 2.0 * M * in_C * Cout * taps)
+
+
+class AnisoConvRowsFn(torch.autograd.Function):
+    """y = relu(scale * conv(x, W) + shift) on channels-last rows for a layer with per-axis ``kernel`` / ``strides`` / ``pads``
+    (as ``core.PackedConv`` describes them); weight [Cout,Cin,kx,ky,kz].  Differentiable in x, W and the conv bias."""
+
+    @staticmethod
+    def forward(ctx, x2d, weight, bias, scale, shift, geom, kernel, strides, pads, relu):
+        B, Xi, Yi, Zi = geom
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        taps = kernel[0] * kernel[1] * kernel[2]
+        assert tuple(weight.shape[2:]) == tuple(kernel), "weight %s is not [Cout,Cin,%d,%d,%d]" % ((tuple(weight.shape),) + tuple(kernel))
+        assert x2d.shape == (B * Xi * Yi * Zi, Cin) and x2d.is_contiguous() and Cin % 4 == 0
+        geom_out = (B,) + out_dims3((Xi, Yi, Zi), kernel, strides, pads)
+        out = torch.empty(geom_out[0] * geom_out[1] * geom_out[2] * geom_out[3], Cout, device=x2d.device, dtype=_F32)
+        eff_shift = shift
+        if bias is not None:    # y = scale * (conv + b) + shift
+            eff_shift = (bias.detach() * scale if scale is not None else bias.detach()) + (shift if shift is not None else 0)
+            eff_shift = eff_shift.float().contiguous()
+        w3 = weight.detach().float().contiguous().view(Cout, Cin, taps)
+        if _h2_direct(Cin, 2.0 * out.shape[0] * Cin * Cout * taps):
+            _conv_launch3(_rows_h2(x2d, Cin), Cin, pack_weights_h2_dev(w3, Cout, Cin, taps, 0), out, Cout, taps, geom, geom_out, kernel,
+                          strides, pads, scale, eff_shift, relu, h2_alpha=1.0)
+        else:
+            _conv_launch3(x2d, Cin, pack_weights_dev(w3, Cout, Cin, taps, 0), out, Cout, taps, geom, geom_out, kernel, strides, pads,
+                          scale, eff_shift, relu)
+        ctx.save_for_backward(x2d, weight, out, scale if scale is not None else torch.empty(0, device=x2d.device))
+        ctx.cfg = (geom, geom_out, kernel, strides, pads, relu, bias is not None, scale is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import core
+        x2d, weight, out, scale = ctx.saved_tensors
+        geom, geom_out, kernel, strides, pads, relu, has_bias, has_scale = ctx.cfg
+        scale = scale if has_scale else None
+        B, Xi, Yi, Zi = geom
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        taps = kernel[0] * kernel[1] * kernel[2]
+        Mo, Mi = out.shape[0], x2d.shape[0]
+        dev = x2d.device
+        dout = dout.float().contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        unit = strides == (1, 1, 1)
+        Cp = _pad4(Cout)
+        dacc = torch.zeros(Mo, Cp, device=dev, dtype=_F32) if Cp != Cout else torch.empty(Mo, Cp, device=dev, dtype=_F32)
+        dbias = torch.empty(Cout, device=dev, dtype=_F32) if (has_bias and need_b) else None
+        ws = workspace(dev)
+        # split-f16 stride-1 dgrad: the gradient operand's power-of-two scale is chosen on the device (see TRAIN_H2_DGRAD)
+        gscale = None
+        if core.CONV_ENGINE == "h2" and TRAIN_H2_DGRAD and need_x and unit and Cp == Cout and Cout % 32 == 0 and Cin % 4 == 0:
+            gscale = torch.empty(2, device=dev, dtype=_F32)
+        call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cp,
+             None, Cout, 0, ptr(dbias), 0, ptr(ws), ws.numel(), ptr(_amax_word(dev)) if gscale is not None else None,
+             ptr(gscale), TRAIN_H2_GRAD_TARGET)
+        if dbias is not None and scale is not None:
+            dbias = dbias * scale
+        dx = dw = None
+        w3 = weight.detach().float().contiguous().view(Cout, Cin, taps)
+        if need_x:
+            dx = torch.empty(Mi, Cin, device=dev, dtype=_F32)
+            if unit:
+                # dx = conv(dacc, W') with every tap axis flipped (pack mode 2 reverses the mixed-radix tap index = each axis) and
+                # pad' = k - 1 - pad per axis
+                pd = tuple(k - 1 - p for k, p in zip(kernel, pads))
+                if gscale is not None and _h2_direct(Cout, 2.0 * Mi * Cin * Cout * taps):
+                    _conv_launch3(_rows_h2(dacc, Cout, gscale), Cout, pack_weights_h2_dev(w3, Cout, Cin, taps, 2), dx, Cin, taps,
+                                  geom_out, geom, kernel, strides, pd, None, None, False, tag="conv_dgrad", h2_alpha=1.0,
+                                  alpha_dev=ptr(gscale, offset=1))
+                else:
+                    _conv_launch3(dacc, Cp, pack_weights_dev(w3, Cout, Cin, taps, 2), dx, Cin, taps, geom_out, geom, kernel, strides,
+                                  pd, None, None, False, tag="conv_dgrad")
+            else:
+                dx.zero_()          # voxels no output reads (stride 4, k = 3: every fourth column and row) keep a zero gradient
+                for rows_c, taps_c, table_c in dgrad_classes3(dev, B, Xi, Yi, Zi, kernel, strides, pads):
+                    wp = pack_weights_dev(w3.index_select(2, taps_c), Cout, Cin, taps_c.numel(), 3)
+                    _conv_launch(dacc, Cp, wp, dx, Cin, taps_c.numel(), geom_out, geom, max(kernel), max(strides), max(pads), None, None,
+                                 None, False, table=table_c, tag="conv_dgrad", out_rows=rows_c)
+        if need_w:
+            idx, tb_live = live_taps3(dev, B, Xi, Yi, Zi, kernel, strides, pads)
+            nl = idx.numel()
+            dw_live = torch.empty(Cout, Cin, nl, device=dev, dtype=_F32)
+            with _lib.TIMER.region("k_wgrad", 2.0 * Mo * Cin * Cout * nl):
+                call("coocc_conv_wgrad", ptr(x2d), Mi, Cin, ptr(dacc), Cp, ptr(tb_live), Mo, Cin, Cout, nl, ptr(dw_live), 0, ptr(ws),
+                     ws.numel())
+            if nl < taps:       # taps that only ever read padding on this grid: zero gradient
+                dw = torch.zeros(Cout, Cin, taps, device=dev, dtype=_F32)
+                dw.index_copy_(2, idx, dw_live)
+            else:
+                dw = dw_live
+            dw = dw.view(weight.shape)
+        return dx, dw, dbias, None, None, None, None, None, None, None
+
+
+def _triple_is_cubic(kernel, strides, pads):
+    return len(set(kernel)) == 1 and len(set(strides)) == 1 and len(set(pads)) == 1
+
+
+def conv3_bn_rows(x2d, weight, geom, kernel, strides=(1, 1, 1), pads=None, bn=None, bias=None, relu=True, sync=None):
+    """``conv_bn_rows`` for a layer given by per-axis triples; ``weight`` [Cout,Cin,kx,ky,kz] (any strides: a permuted view of a
+    reference [.,.,kz,ky,kx] parameter keeps its gradient).  Cubic triples take ``conv_bn_rows`` (ConvRowsFn and its Winograd
+    routes).  Every BN follows its own ``training`` flag."""
+    kernel, strides = tuple(int(k) for k in kernel), tuple(int(s) for s in strides)
+    pads = tuple(int(p) for p in pads) if pads is not None else tuple((k - 1) // 2 for k in kernel)
+    if _triple_is_cubic(kernel, strides, pads):
+        return conv_bn_rows(x2d, weight, geom, bn=bn, bias=bias, stride=strides[0], pad=pads[0], relu=relu)
+    B, X, Y, Z = geom
+    go = (B,) + out_dims3((X, Y, Z), kernel, strides, pads)
+    x2d = x2d.contiguous()
+    if bn is not None and bn.training:
+        y = AnisoConvRowsFn.apply(x2d, weight, bias, None, None, tuple(geom), kernel, strides, pads, False)
+        return BatchNormRowsFn.apply(y, bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync)), go
+    scale = shift = None
+    if bn is not None:
+        from .core import fold_bn
+        s, b = fold_bn(bn, None)
+        scale, shift = s.to(x2d.device).contiguous(), b.to(x2d.device).contiguous()
+    return AnisoConvRowsFn.apply(x2d, weight, bias, scale, shift, tuple(geom), kernel, strides, pads, relu), go
+
+
+class FpnSumFn(torch.autograd.Function):
+    """``lidar_trunk.fpn_sum`` on 2-D tensors: ups[l] [B*(X/s)*(Y/s)*Z, s*s*C] (child-major deblock outputs) -> [B*X*Y*Z, C].  The
+    backward re-lays dout into every level's own layout (coocc_fpn_sum_bwd); a stride-1 level's gradient is dout itself."""
+
+    @staticmethod
+    def forward(ctx, geom, strides, C, *ups):
+        import ctypes
+        B, X, Y, Z = geom
+        ups = [u.float().contiguous() for u in ups]
+        for u, s in zip(ups, strides):
+            assert u.shape == (B * (X // s) * (Y // s) * Z, s * s * C) and X % s == 0 and Y % s == 0, "level sizes differ after upsampling"
+        out = torch.empty(B * X * Y * Z, C, device=ups[0].device, dtype=_F32)
+        pp = (ctypes.c_void_p * 4)(*[u.data_ptr() for u in ups])
+        ss = (ctypes.c_int * 4)(*strides)
+        with _lib.TIMER.region("k_fpn_sum", 4.0 * out.numel() * (len(ups) + 1)):
+            call("coocc_fpn_sum", pp, ss, len(ups), B, X, Y, Z, C, ptr(out), C, None)
+        ctx.cfg = (geom, tuple(strides), C)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        import ctypes
+        (B, X, Y, Z), strides, C = ctx.cfg
+        dout = dout.float().contiguous()
+        need = ctx.needs_input_grad[3:]
+        grads = [None if (s == 1 or not n) else torch.empty(B * (X // s) * (Y // s) * Z, s * s * C, device=dout.device, dtype=_F32)
+                 for s, n in zip(strides, need)]
+        if any(g is not None for g in grads):
+            pp = (ctypes.c_void_p * 4)(*[g.data_ptr() if g is not None else None for g in grads])
+            ss = (ctypes.c_int * 4)(*strides)
+            with _lib.TIMER.region("k_fpn_sum_bwd", 4.0 * dout.numel() * (1 + sum(g is not None for g in grads))):
+                call("coocc_fpn_sum_bwd", ptr(dout), C, pp, ss, len(strides), B, X, Y, Z, C)
+        return (None, None, None) + tuple(dout if (s == 1 and n) else g for s, n, g in zip(strides, need, grads))
+
+
+def fpn_sum_rows(ups, strides, C, geom):
+    return FpnSumFn.apply(tuple(geom), tuple(int(s) for s in strides), int(C), *ups)
+
+
+def deconv_bn_rows(x2d, up, bn, s, relu=True, sync=None):
+    """A SECOND3DFPN deblock -- nn.ConvTranspose3d(kernel = stride = (1,s,s)) -> BN3d -> ReLU (second3d_fpn.py:47-69) -- on the COARSE
+    rows [M, Cin] -> [M, s*s*Cout] (child (kx, ky) of a coarse voxel at columns (kx*s + ky)*Cout ..): the pointwise GEMM with
+    ``core.deconv_weight``'s layout taken as a differentiable view of the parameter (so the weight gradient lands in the module's
+    [Cin,Cout,1,s,s] tensor), then the norm layer in its own mode.  One BN channel serves the s*s children of a coarse voxel, so
+    batch statistics over the [M*s*s, Cout] view of the GEMM's output are those of the upsampled volume; a BN in eval mode is folded
+    into the GEMM's epilogue with its scale / shift repeated s*s times."""
+    cin, cout = up.weight.shape[:2]
+    assert tuple(up.weight.shape[2:]) == (1, s, s), "deconv kernel %s is not (1,%d,%d)" % (tuple(up.weight.shape[2:]), s, s)
+    w = up.weight[:, :, 0].permute(3, 2, 1, 0).reshape(s * s * cout, cin)
+    b = up.bias.repeat(s * s) if up.bias is not None else None
+    n = x2d.shape[0]
+    if bn is not None and bn.training:
+        y = linear_rows(x2d, w, b, relu=False)
+        y = BatchNormRowsFn.apply(y.view(n * s * s, cout), bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync))
+        return y.view(n, s * s * cout)
+    scale = shift = None
+    if bn is not None:
+        from .core import fold_bn
+        sc, sh = fold_bn(bn, None)
+        scale, shift = sc.repeat(s * s).to(x2d.device).contiguous(), sh.repeat(s * s).to(x2d.device).contiguous()
+    return ConvRowsFn.apply(x2d.contiguous(), w, b, None, scale, shift, (1, n, 1, 1), 1, 1, 0, relu)
+
+
+class ZyxRowsFn(torch.autograd.Function):
+    """The trunk's entry transposition [B,C,Z,Y,X] -> rows in (b, x, y, z) order (coocc_zyx_to_rows) with its gradient: the
+    permuted view of the row gradient, no kernel."""
+
+    @staticmethod
+    def forward(ctx, x):
+        from .lidar_trunk import bczyx_to_rows
+        r = bczyx_to_rows(x.detach())
+        ctx.cfg = (r.B, r.X, r.Y, r.Z, r.C)
+        t = r.t if (r.coff == 0 and r.stride == r.C) else r.t[:, r.coff:r.coff + r.C].contiguous()
+        return t.clone() if t.data_ptr() == x.data_ptr() else t      # channels-last memory: a view of the input itself
+
+    @staticmethod
+    def backward(ctx, drows):
+        B, X, Y, Z, C = ctx.cfg
+        return drows.view(B, X, Y, Z, C).permute(0, 4, 3, 2, 1)
+
+
+def _zyx(w):
+    """A reference conv weight [N,C,kz,ky,kx] in the [N,C,kx,ky,kz] order this package's taps read (``core.zyx_weight`` without the
+    detach: the gradient flows back to the parameter)."""
+    return w.permute(0, 1, 4, 3, 2).contiguous()
+
+
+def second3d_forward_train(backbone, x2d, geom):
+    """SECOND3D (second3d.py:91-114) on rows -> [(rows, geom)] per block; the inference module's own parameters."""
+    kz, ky, kx = backbone.kernel
+    outs = []
+    for i, blk in enumerate(backbone.blocks):
+        s = backbone.layer_strides[i]
+        h, g = x2d, geom
+        for j in range(0, len(blk), 3):
+            st = (s, s, 1) if j == 0 else (1, 1, 1)
+            h, g = conv3_bn_rows(h, _zyx(blk[j].weight), g, (kx, ky, kz), st, bn=blk[j + 1], bias=blk[j].bias, relu=True)
+        outs.append((h, g))
+        if backbone.is_cascade:
+            x2d, geom = h, g
+    return outs
+
+
+def second3dfpn_forward_train(neck, feats):
+    """SECOND3DFPN (second3d_fpn.py:108-143) on [(rows, geom)] -> (rows, geom)."""
+    from torch import nn
+    assert len(feats) == len(neck.in_channels)
+    C = neck.out_channels[-1]
+    ups, fine = [], None
+    for (x, g), s, blk in zip(feats, neck.upsample_strides, neck.deblocks):
+        up, bn = blk[0], blk[1]
+        if isinstance(up, nn.ConvTranspose3d):
+            ups.append(deconv_bn_rows(x, up, bn, s))
+        else:
+            ups.append(conv_bn_rows(x, up.weight, g, bn=bn, bias=up.bias, relu=True)[0])
+        gf = (g[0], g[1] * s, g[2] * s, g[3])
+        if fine is not None and gf != fine:
+            raise ValueError("SECOND3DFPN: level sizes differ after upsampling (%s vs %s)" % (gf[1:], fine[1:]))
+        fine = gf
+    if len(ups) == 1 and neck.upsample_strides[0] == 1:
+        out = ups[0]                                                            # second3d_fpn.py:123-124
+    else:
+        out = fpn_sum_rows(ups, neck.upsample_strides, C, fine)
+    if neck.extra_conv is not None:
+        kz, ky, kx = neck.extra_kernel
+        for j in range(0, len(neck.extra_blocks), 3):
+            c, bn = neck.extra_blocks[j], neck.extra_blocks[j + 1]
+            out, fine = conv3_bn_rows(out, _zyx(c.weight), fine, (kx, ky, kz), bn=bn, bias=c.bias, relu=True)
+    return out, fine

@@ -104,7 +104,7 @@ class COOCC_Ray(nn.Module):
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
-                 **kwargs):
+                 train_lidar_trunk=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -116,6 +116,9 @@ class COOCC_Ray(nn.Module):
         # opt-in: a ``pts_middle_encoder`` of type SparseEncoderHD (coocc_lidar.py) is built from ``lidar_hd`` -- the HIP sparse
         # engine -- instead of staying upstream (spconv v1, which does not build on ROCm)
         self.sparse_encoder_hd = bool(sparse_encoder_hd)
+        # opt-in (COOCC_Ray_L): under train() the dense LiDAR trunk SECOND3D + SECOND3DFPN runs its differentiable form
+        # (lidar_trunk.run_trunk_train) and forward_train takes pts_middle_feats / raw points; detectors without that trunk ignore it
+        self.train_lidar_trunk = bool(train_lidar_trunk)
         if pts_middle_encoder:
             if self.sparse_encoder_hd and pts_middle_encoder.get("type") == "SparseEncoderHD":
                 if not self.TAKES_SPARSE_ENCODER_HD:
@@ -680,7 +683,10 @@ class COOCC_Ray_L(COOCC_Ray):
     registries and runs on the HIP engine (``lidar_trunk``).  The ``SparseEncoderHD`` middle encoder in front of it is built from
     ``lidar_hd`` (the HIP sparse engine) under ``sparse_encoder_hd=True`` -- the model then runs from a raw point cloud: eager
     voxelise -> VFE -> encoder -> trunk, then the decoder; by default it is left to the caller as before (an injected module, or
-    ``external_encoders``); ``precomputed=dict(pts_middle_feats=...)`` (its dense [B,C,Z,Y,X] output) runs the trunk without it."""
+    ``external_encoders``); ``precomputed=dict(pts_middle_feats=...)`` (its dense [B,C,Z,Y,X] output) runs the trunk without it.
+    ``train_lidar_trunk=True``: under ``train()`` the trunk runs ``lidar_trunk.run_trunk_train`` (batch-statistics BN, gradients to
+    every trunk parameter) and ``forward_train`` takes ``pts_middle_feats``, or raw ``points`` with the sparse middle encoder frozen
+    (``freeze_lidar_encoder()``: ``SparseEncoderHD`` itself stays eval-only)."""
     WITH_RGB_HEAD = False
     DEPTH_GT_INDEX = -2
     TAKES_SPARSE_ENCODER_HD = True
@@ -691,6 +697,10 @@ class COOCC_Ray_L(COOCC_Ray):
         trunk stays on channels-last rows: one entry transposition at most, no conversion towards the fuser / encoder."""
         from . import lidar_trunk as lt
         if isinstance(self.pts_backbone, lt.SECOND3D) and isinstance(self.pts_neck, lt.SECOND3DFPN):
+            if self.train_lidar_trunk and self.training:
+                # training (opt-in): the differentiable trunk; the views below keep the graph (view + permute of rows with a grad_fn)
+                rows = lt.run_trunk_train(self.pts_backbone, self.pts_neck, x)
+                return rows.as_ncdhw(), [lt.rows_as_bczyx(rows)]
             rows = lt.run_trunk(self.pts_backbone, self.pts_neck, x)
             return rows.as_ncdhw(), [lt.rows_as_bczyx(rows)]
         if self.pts_backbone is not None:
@@ -731,8 +741,11 @@ class COOCC_Ray_L(COOCC_Ray):
     def forward_train(self, points=None, img_metas=None, img_inputs=None, gt_occ=None, points_occ=None, visible_mask=None,
                       gt_depths=None, precomputed=None, generator=None, **kwargs):
         if precomputed is not None and precomputed.get("pts_middle_feats") is not None:
-            raise NotImplementedError("COOCC_Ray_L.forward_train: precomputed pts_middle_feats would run SECOND3D / SECOND3DFPN in "
-                                      "training mode, which is not built; feed pts_voxel_feats")
+            if not self.train_lidar_trunk:
+                raise NotImplementedError("COOCC_Ray_L.forward_train: precomputed pts_middle_feats would run SECOND3D / SECOND3DFPN in "
+                                          "training mode, which this detector was not built for (train_lidar_trunk=True); feed "
+                                          "pts_voxel_feats")
+            precomputed = self._with_trunk(precomputed)
         return super().forward_train(points, img_metas, img_inputs, gt_occ, points_occ, visible_mask, gt_depths, precomputed,
                                      generator, **kwargs)
 

@@ -8,7 +8,8 @@ the reference's kernel (1,3,3) is this package's 3x3x1 (Winograd F(m x m,3x3) ov
 grids, the direct split-f16 kernels below the row threshold and for the (s,s,1)-strided first convs).  The neck's
 ConvTranspose3d(kernel = stride = (1,s,s)) layers have no overlap: each is a pointwise GEMM Cin -> s*s*Cout on the coarse
 rows, and ``coocc_fpn_sum`` (csrc/second_fpn.hip) gathers the children and adds the levels in the reference's order.
-Eval mode only (folded BN); there is no CPU or eager-PyTorch fallback.
+The modules' own ``forward`` is eval mode only (folded BN); ``run_trunk_train`` is the differentiable trunk (batch-statistics BN,
+dgrad / wgrad of every layer: ``autograd``).  There is no CPU or eager-PyTorch fallback.
 """
 import ctypes
 
@@ -318,3 +319,31 @@ def run_trunk(backbone, neck, x):
     layers write the H2 operands of the neck's deblocks in their epilogues."""
     feats = backbone.forward_rows(bczyx_to_rows(x), readers=neck.reader_packs())
     return neck.forward_rows(feats)
+
+
+def run_trunk_train(backbone, neck, x):
+    """Differentiable ``neck(backbone(x))``: x = [B,C,Z,Y,X] tensor (or Rows) -> Rows of the neck's output whose ``t`` carries a
+    ``grad_fn``.  Every layer is an autograd Function over the HIP kernels (``autograd.second3d_forward_train`` /
+    ``second3dfpn_forward_train``); every BN follows its own ``training`` flag -- batch (or SyncBN all-reduced) statistics and
+    running-statistics updates under ``train()``, folded running statistics in eval mode.  The modules are the inference modules:
+    parameters and state_dict keys are shared, and ``run_trunk`` re-packs from the stepped parameters afterwards (``PackCache``)."""
+    from . import autograd as ag
+    if isinstance(x, Rows):
+        r = x
+        x2d = r.t if (r.coff == 0 and r.stride == r.C) else r.t[:, r.coff:r.coff + r.C].contiguous()
+        geom = (r.B, r.X, r.Y, r.Z)
+    else:
+        if not torch.is_tensor(x) or x.dim() != 5:
+            raise ValueError("expected a [B,C,Z,Y,X] tensor")
+        if not x.is_cuda:
+            raise _lib.CooccError("co_occ_amd modules run on the GPU only (no CPU fallback)")
+        B, C, Z, Y, X = x.shape
+        geom = (B, X, Y, Z)
+        if x.requires_grad:
+            x2d = ag.ZyxRowsFn.apply(x)
+        else:
+            r = bczyx_to_rows(x)
+            x2d = r.t if (r.coff == 0 and r.stride == r.C) else r.t[:, r.coff:r.coff + r.C].contiguous()
+    feats = ag.second3d_forward_train(backbone, x2d, geom)
+    out, g = ag.second3dfpn_forward_train(neck, feats)
+    return Rows(out, g[0], g[1], g[2], g[3], out.shape[1])

@@ -73,7 +73,7 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
     return DETECTORS.build(dict(cfg, **overrides))
 
 
-def register_into_mmdet(detectors=False, sparse_encoder_hd=False):
+def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -81,7 +81,11 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False):
     encoders, losses and metrics.  ``detectors=True`` additionally replaces ``COOCC_Ray`` / ``COOCC_Ray_L`` with ours (HIP
     render block, on-device metrics; its image encoder is built back through these same registries).
     ``sparse_encoder_hd=True`` additionally replaces mmdet3d's ``SparseEncoderHD`` middle encoder (spconv v1) with
-    ``lidar_hd.SparseEncoderHD``.  Returns False when mmdet / mmdet3d are not importable."""
+    ``lidar_hd.SparseEncoderHD``.  ``train_lidar_trunk=True`` (with ``detectors=True``: the option is the detector's) registers
+    ``COOCC_Ray_L`` with its ``train_lidar_trunk`` option on by default, so an unchanged coocc_lidar.py config trains SECOND3D /
+    SECOND3DFPN on the HIP engine.  Returns False when mmdet / mmdet3d are not importable."""
+    if train_lidar_trunk and not detectors:
+        raise ValueError("register_into_mmdet: train_lidar_trunk=True is an option of this package's COOCC_Ray_L; pass detectors=True")
     try:
         from mmdet.models import builder as mb
         from mmdet3d.models import builder as m3b
@@ -98,4 +102,18 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False):
     for ours, theirs in pairs:
         for k, cls in ours.module_dict.items():
             theirs.register_module(name=k, force=True, module=cls)
+    if train_lidar_trunk:
+        mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True, module=trunk_training_detector())
     return True
+
+
+def trunk_training_detector():
+    """``COOCC_Ray_L`` whose ``train_lidar_trunk`` option defaults to on (what ``register_into_mmdet(train_lidar_trunk=True)`` puts
+    into mmdet's registry under the reference name)."""
+    base = DETECTORS.get("COOCC_Ray_L")
+
+    class COOCC_Ray_L(base):
+        def __init__(self, *args, train_lidar_trunk=True, **kwargs):
+            super().__init__(*args, train_lidar_trunk=train_lidar_trunk, **kwargs)
+    COOCC_Ray_L.__qualname__ = "COOCC_Ray_L"
+    return COOCC_Ray_L

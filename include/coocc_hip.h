@@ -846,6 +846,21 @@ int coocc_fpn_sum(const float* const* ups, const int* strides, int levels, int B
 int coocc_zyx_to_rows(const float* src, float* dst, int B, int C, int Z, int Y, int X, int dst_stride, int dst_coff,
                       void* stream);
 
+/* ---- training of that trunk (co_occ_amd/lidar_trunk.py run_trunk_train; torch.autograd through cuDNN / MIOpen upstream) */
+/* coocc_conv_tap_table with per-axis kernel (kx,ky,kz), stride (sx,sy,sz) and padding (px,py,pz): the row tables of SECOND3D's
+ * 3x3x1 convolutions with strides (s,s,1) (second3d.py:52-77).  Same conventions: table[taps][M] int32, tap t = (dx*ky + dy)*kz + dz,
+ * rows in (b,x,y,z) order; dgrad == 0: M = B*Xo*Yo*Zo, the input row output o reads through tap t (-1 = padding); dgrad != 0:
+ * M = B*Xi*Yi*Zi, the output row o with o*s - p + d == i per axis (-1 = none: with s > k - 1 some input voxels are read by no
+ * output at all).  For cubic arguments the table of coocc_conv_tap_table.  The extents are checked against (n + 2p - k)/s + 1. */
+int coocc_conv_tap_table3(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int kx, int ky, int kz, int sx, int sy, int sz,
+                          int px, int py, int pz, int dgrad, int32_t* table, void* stream);
+/* Backward of coocc_fpn_sum: every level's gradient is dout [B*X*Y*Z][dout_stride] (C channels) re-laid into that deblock's own
+ * child-major rows, dups[l][B*(X/s)*(Y/s)*Z][s*s][C], child (x%s)*s + y%s.  dout is read once (16-byte accesses) for all levels; no
+ * arithmetic, bit-exact.  dups / strides: HOST arrays of `levels` (1-4) device pointers / strides (1, 2, 4, 8); a NULL level is
+ * skipped (a stride-1 level's gradient is dout itself).  C % 4 == 0. */
+int coocc_fpn_sum_bwd(const float* dout, int dout_stride, float* const* dups, const int* strides, int levels, int B, int X, int Y,
+                      int Z, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
