@@ -954,10 +954,12 @@ class BatchNormRowsFn(torch.autograd.Function):
     """Training-mode BatchNorm3d / SyncBN on rows [M, C] (+ residual, ReLU): batch mean / biased variance, running
     statistics updated in place like torch (momentum, unbiased variance).  With a process group the statistics are
     those of all ranks' rows (one all-reduce of 2C+1 floats in the forward, one of 2C in the backward, as
-    torch.nn.SyncBatchNorm does); the returned dgamma / dbeta are this rank's share, which DDP then reduces."""
+    torch.nn.SyncBatchNorm does); the returned dgamma / dbeta are this rank's share, which DDP then reduces.
+    ``out_h2``: optional [M, C] fp32-sized buffer (C % 32 == 0) the apply pass fills with the split-f16 twin of y
+    (coocc_bn_apply_ex: the operand of a following split-f16 GEMM, no coocc_rows_to_h2 launch)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, res, bn, relu, group=None):
+    def forward(ctx, x, gamma, beta, res, bn, relu, group=None, out_h2=None):
         x = x.float().contiguous()
         M, C = x.shape
         dev = x.device
@@ -977,8 +979,12 @@ class BatchNormRowsFn(torch.autograd.Function):
             var = (pack[C:2 * C] / count - gm * gm).clamp_(min=0).float()
         y = torch.empty_like(x)
         g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        call("coocc_bn_apply", ptr(x), M, C, ptr(mean), ptr(var), ptr(g), ptr(b), float(bn.eps),
-             ptr(res.float().contiguous()) if res is not None else None, int(relu), ptr(y))
+        if out_h2 is not None:
+            call("coocc_bn_apply_ex", ptr(x), M, C, ptr(mean), ptr(var), ptr(g), ptr(b), float(bn.eps),
+                 ptr(res.float().contiguous()) if res is not None else None, int(relu), ptr(y), ptr(out_h2))
+        else:
+            call("coocc_bn_apply", ptr(x), M, C, ptr(mean), ptr(var), ptr(g), ptr(b), float(bn.eps),
+                 ptr(res.float().contiguous()) if res is not None else None, int(relu), ptr(y))
         if bn.track_running_stats and bn.running_mean is not None:
             with torch.no_grad():
                 bn.num_batches_tracked += 1          # torch increments first; momentum=None = cumulative moving average
@@ -1009,7 +1015,7 @@ class BatchNormRowsFn(torch.autograd.Function):
             dist.all_reduce(tot, group=group)
         call("coocc_bn_backward_dx", ptr(x), ptr(y), ptr(dy), M, C, ptr(mean), ptr(var), ptr(g), eps, relu, ptr(tot[0]), ptr(tot[1]),
              float(count), ptr(dx), ptr(dres))
-        return dx, sums[0], sums[1], dres, None, None, None
+        return dx, sums[0], sums[1], dres, None, None, None, None
 
 
 def conv3d_bn_train_rows(x2d, weight, geom, bn, stride=1, pad=None, relu=True, res2d=None, bias=None, sync=None):

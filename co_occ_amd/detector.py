@@ -104,7 +104,7 @@ class COOCC_Ray(nn.Module):
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
-                 train_lidar_trunk=False, **kwargs):
+                 train_lidar_trunk=False, train_sparse_encoder_hd=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -119,6 +119,9 @@ class COOCC_Ray(nn.Module):
         # opt-in (COOCC_Ray_L): under train() the dense LiDAR trunk SECOND3D + SECOND3DFPN runs its differentiable form
         # (lidar_trunk.run_trunk_train) and forward_train takes pts_middle_feats / raw points; detectors without that trunk ignore it
         self.train_lidar_trunk = bool(train_lidar_trunk)
+        # opt-in (COOCC_Ray_L with sparse_encoder_hd=True): ``SparseEncoderHD`` runs its differentiable forward under train()
+        # (lidar_hd ``train_enabled``: batch-statistics BN1d, gradients through the rule books); detectors without it ignore the key
+        self.train_sparse_encoder_hd = bool(train_sparse_encoder_hd)
         if pts_middle_encoder:
             if self.sparse_encoder_hd and pts_middle_encoder.get("type") == "SparseEncoderHD":
                 if not self.TAKES_SPARSE_ENCODER_HD:
@@ -127,6 +130,7 @@ class COOCC_Ray(nn.Module):
                                               "extract_pts_feat does not take (upstream's neither); use COOCC_Ray_L" % type(self).__name__)
                 from . import lidar_hd
                 self.pts_middle_encoder = lidar_hd.MIDDLE_ENCODERS_HD.build(pts_middle_encoder)
+                self.pts_middle_encoder.train_enabled = self.train_sparse_encoder_hd
             elif pts_middle_encoder.get("type") in lidar.MIDDLE_ENCODERS:
                 # trains like upstream (sparse_lidar_enc.py:125-176; batch-statistics BN1d, gradients through the rule books:
                 # co_occ_amd/lidar.py ``SparseConvFn``); ``freeze_lidar_encoder()`` restores the round-2..4 behaviour
@@ -685,8 +689,10 @@ class COOCC_Ray_L(COOCC_Ray):
     voxelise -> VFE -> encoder -> trunk, then the decoder; by default it is left to the caller as before (an injected module, or
     ``external_encoders``); ``precomputed=dict(pts_middle_feats=...)`` (its dense [B,C,Z,Y,X] output) runs the trunk without it.
     ``train_lidar_trunk=True``: under ``train()`` the trunk runs ``lidar_trunk.run_trunk_train`` (batch-statistics BN, gradients to
-    every trunk parameter) and ``forward_train`` takes ``pts_middle_feats``, or raw ``points`` with the sparse middle encoder frozen
-    (``freeze_lidar_encoder()``: ``SparseEncoderHD`` itself stays eval-only)."""
+    every trunk parameter) and ``forward_train`` takes ``pts_middle_feats``, or raw ``points``: with the sparse middle encoder frozen
+    (``freeze_lidar_encoder()``: it stays in eval mode and takes no gradient), or -- ``train_sparse_encoder_hd=True`` -- with
+    ``SparseEncoderHD`` training too (``lidar_hd``: batch-statistics BN1d, gradients through the per-axis rule books), so that a
+    step from a raw cloud reaches every ``pts_middle_encoder`` / ``pts_backbone`` / ``pts_neck`` parameter."""
     WITH_RGB_HEAD = False
     DEPTH_GT_INDEX = -2
     TAKES_SPARSE_ENCODER_HD = True
@@ -698,8 +704,10 @@ class COOCC_Ray_L(COOCC_Ray):
         from . import lidar_trunk as lt
         if isinstance(self.pts_backbone, lt.SECOND3D) and isinstance(self.pts_neck, lt.SECOND3DFPN):
             if self.train_lidar_trunk and self.training:
-                # training (opt-in): the differentiable trunk; the views below keep the graph (view + permute of rows with a grad_fn)
-                rows = lt.run_trunk_train(self.pts_backbone, self.pts_neck, x)
+                # training (opt-in): the differentiable trunk; the views below keep the graph (view + permute of rows with a grad_fn).
+                # A view that remembers its rows (SparseEncoderHD's output, with or without a grad_fn) hands them over as they are
+                r = lt.rows_of_bczyx(x) if torch.is_tensor(x) else None
+                rows = lt.run_trunk_train(self.pts_backbone, self.pts_neck, r if r is not None else x)
                 return rows.as_ncdhw(), [lt.rows_as_bczyx(rows)]
             rows = lt.run_trunk(self.pts_backbone, self.pts_neck, x)
             return rows.as_ncdhw(), [lt.rows_as_bczyx(rows)]

@@ -9,7 +9,9 @@ Upstream runs on the spconv v1 that mmdetection3d vendors; its SubMConv3d / Spar
 (``coocc_sparse_conv_table3`` / ``coocc_sparse_down_flags3``: the config's third down-convolution pads ``[0,1,1]``) and the 1x1x1
 ``conv_out``, which writes straight into the zeroed dense volume through the GEMM's ``out_rows`` scatter.
 
-Eval mode, batch size 1.  The class is NOT in ``lidar.MIDDLE_ENCODERS``: the detectors build it only under
+Batch size 1.  Eval mode by default: ``train()`` runs the differentiable forward (batch-statistics BN1d, gradients through the same
+rule books; the section "training" below) only when ``train_enabled`` is set -- what the detectors' ``train_sparse_encoder_hd`` option
+does -- and refuses by name otherwise.  The class is NOT in ``lidar.MIDDLE_ENCODERS``: the detectors build it only under
 ``sparse_encoder_hd=True`` and ``register_into_mmdet(sparse_encoder_hd=True)`` writes it into mmdet3d's registry."""
 import os
 
@@ -199,6 +201,177 @@ class SparseBasicBlockHD(nn.Module):
         self.relu = nn.ReLU(inplace=True)
 
 
+# ----------------------------------------------------------------------------- training (opt-in: SparseEncoderHD.train_enabled)
+# Under ``train()`` every SparseConvV1 is an autograd Function over the level's forward book and a transposed one:
+#   forward  y[o]  = sum_t W_t^T . x[table[t][o]]                row-table GEMM, as inference (no epilogue: BN1d follows)
+#   dgrad    dx[i] = sum_t W_t . dy[bwd[t][i]]                   the same GEMM over the TRANSPOSED book.  SubMConv3d: table.flip(0) (the
+#                                                                active set is its own mirror image); SparseConv3d:
+#                                                                coocc_sparse_dgrad_table3, made on the device from geometry
+#   wgrad    dW_t  = sum_o x[table[t][o]] (x) dy[o]              coocc_conv_wgrad with the forward book (fp32 MFMA on every engine)
+# BN1d = ``autograd.BatchNormRowsFn`` on the active rows (batch statistics, running-statistics updates, residual + ReLU inside); its
+# apply pass writes the split-f16 twin the next GEMM reads (coocc_bn_apply_ex).  conv_out's rows reach the dense volume through
+# ``autograd.ScatterRowsFn``.  The 16-wide first stage trains on 16-wide rows on the fp32-MFMA kernels (no zero-padded columns in
+# training: a padded channel would have to be kept out of every BN statistic), whatever ``wide16`` says for inference.
+# COOCC_HD_TRAIN_H2 (default 1): forward GEMMs with Cin % 32 == 0 and dgrad GEMMs with Cout % 32 == 0 on the split-f16 row-table
+# kernels when COOCC_CONV_ENGINE=h2, COOCC_LIDAR_H2=1 and COOCC_TRAIN_H2=1 (packs made on the device every step, the gradient operand
+# scaled by the device-chosen power of two of autograd.TRAIN_H2_DGRAD); 0 = fp32 MFMA everywhere.  MEASURED at the config's size
+# (120 000 voxels on [65,800,800], forward + backward, profiles/sparse_hd_train_bench.json): 57.3 ms against 66.0 ms, the forward
+# alone 5.1 against 9.2 ms.  Weight gradients are coocc_conv_wgrad (fp32 MFMA) either way and are most of the rest.
+HD_TRAIN_H2 = os.environ.get("COOCC_HD_TRAIN_H2", "1") != "0"
+# 1: the dgrad of a strided SparseConv3d runs as one row-table GEMM per residue class of the input rows over that class's live taps
+# (1, 2, 4 or 8 of 27 at stride 2); 0: one launch over all taps of the full transposed book (7/8 of whose entries are -1 at stride
+# 2).  Same values up to summation order.  MEASURED, same run: the backward takes 52.2 ms either way -- the row-table kernels skip
+# a -1 entry cheaply, so 27 mostly empty taps cost no more than eight launches over 1-8 full ones -- while the class lists (a stable
+# sort, one host read, the gathers of the sub-tables: 0.50-0.59 ms per down-convolution against 0.02-0.04 ms for the book alone) add
+# 1.7 ms to the forward: 59.0 against 57.3 ms per step.  So the default is 0, not the dense path's choice carried over.
+HD_DGRAD_CLASSES = os.environ.get("COOCC_HD_DGRAD_CLASSES", "0") != "0"
+
+
+def _train_h2():
+    from . import autograd as ag
+    return HD_TRAIN_H2 and core.CONV_ENGINE == "h2" and lidar.LIDAR_H2 and ag.TRAIN_H2
+
+
+def class_taps(cls, kernel, stride):
+    """Taps t = (kd*ky + kh)*kx + kw that can reach an input row of residue class ``cls`` = (rz*sy + ry)*sx + rx: the output
+    coordinate (c + p - k) / s is whole on an axis iff k = (c + p) mod s there."""
+    rx, ry, rz = cls % stride[2], (cls // stride[2]) % stride[1], cls // (stride[2] * stride[1])
+    return [(kd * kernel[1] + kh) * kernel[2] + kw for kd in range(kernel[0]) for kh in range(kernel[1]) for kw in range(kernel[2])
+            if kd % stride[0] == rz and kh % stride[1] == ry and kw % stride[2] == rx]
+
+
+def dgrad_books(level, out_level, kernel, stride, pad, by_class=None):
+    """Transposed rule book of the SparseConv3d(kernel, stride, pad) that made ``out_level`` from ``level``:
+    (table [taps, Mi] int32, class ids [Mi] int32, classes).  ``classes``: None, or (``by_class``, default COOCC_HD_DGRAD_CLASSES,
+    and a stride above 1) the list of (rows int32 [Mc], taps int64 [Tc], table int32 [Tc, Mc]) over the classes that have rows and
+    taps -- rows from a stable device sort of the class ids and ONE host read of the class counts."""
+    kernel, stride, pad = tuple(kernel), tuple(stride), tuple(pad)
+    dev = level.coors.device
+    taps, Mi = kernel[0] * kernel[1] * kernel[2], level.M
+    table = torch.empty(taps, Mi, device=dev, dtype=_I32)
+    cls = torch.empty(Mi, device=dev, dtype=_I32)
+    if Mi:
+        call("coocc_sparse_dgrad_table3", ptr(level.coors), Mi, *level.shape, *kernel, *stride, *pad, *out_level.shape,
+             ptr(out_level.index_map()), ptr(table), ptr(cls))
+    if by_class is None:
+        by_class = HD_DGRAD_CLASSES
+    if not by_class or stride == (1, 1, 1):
+        return table, cls, None
+    classes = []
+    if Mi and out_level.M:
+        ncls = stride[0] * stride[1] * stride[2]
+        order = torch.sort(cls, stable=True).indices
+        counts = _lib.host_read(torch.bincount(cls, minlength=ncls))
+        start = 0
+        for c, n in enumerate(counts):
+            live = class_taps(c, kernel, stride)
+            if n and live:
+                rows = order[start:start + n]
+                t_idx = torch.tensor(live, device=dev)
+                classes.append((rows.int().contiguous(), t_idx, table.index_select(0, t_idx).index_select(1, rows).contiguous()))
+            start += n
+    return table, cls, classes
+
+
+class SparseConvV1Fn(torch.autograd.Function):
+    """y = relu(scale * sparse_conv(x; W, table) + shift + res): SubMConv3d / SparseConv3d of spconv v1 on rows, differentiable in
+    x, W and res.  ``weight``: [kd, kh, kw, Cin, Cout] (upstream's state_dict layout; dW comes back in it); x: [n_in, pad4(Cin)];
+    ``bwd``: the transposed book [taps, n_in], or the class list of ``dgrad_books``; ``x_h2``: the split-f16 twin of x when its
+    producer wrote one; scale / shift: constants (an eval-mode BN folded into the epilogue) or None."""
+
+    @staticmethod
+    def forward(ctx, x, weight, table, bwd, x_h2, scale, shift, res, relu):
+        from . import autograd as ag
+        taps, Mo = table.shape
+        Cin, Cout = weight.shape[3], weight.shape[4]
+        n_in, Cp = x.shape
+        assert weight.shape[0] * weight.shape[1] * weight.shape[2] == taps and Cp == lidar._pad4(Cin) and Cout % 4 == 0
+        w3 = weight.detach().float().reshape(taps, Cin, Cout).permute(2, 1, 0)                 # [Cout, Cin, taps]
+        if Cp != Cin:
+            w3 = torch.cat([w3, w3.new_zeros(Cout, Cp - Cin, taps)], 1)
+        w3 = w3.contiguous()
+        out = torch.empty(Mo, Cout, device=x.device, dtype=_F32)
+        h2 = _train_h2()
+        if Mo:
+            geo = ((1, n_in, 1, 1), (1, Mo, 1, 1), 1, 1, 0, scale, shift, res, relu)
+            if h2 and Cp % 32 == 0:
+                xh = x_h2 if x_h2 is not None else ag._rows_h2(x, Cp)
+                ag._conv_launch(xh, Cp, ag.pack_weights_h2_dev(w3, Cout, Cp, taps, 0), out, Cout, taps, *geo, table=table,
+                                tag="sparse_hd_fwd", h2_alpha=1.0)
+            else:
+                ag._conv_launch(x, Cp, ag.pack_weights_dev(w3, Cout, Cp, taps, 0), out, Cout, taps, *geo, table=table, tag="sparse_hd_fwd")
+        ctx.save_for_backward(x, w3, table, out if relu else None, scale, *(bwd if torch.is_tensor(bwd) else [t for c in bwd for t in c]))
+        ctx.cfg = (Cin, tuple(weight.shape), torch.is_tensor(bwd), h2, bool(relu), res is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import autograd as ag
+        x, w3, table, out, scale = ctx.saved_tensors[:5]
+        books = ctx.saved_tensors[5:]
+        Cin, wshape, full, h2, relu, has_res = ctx.cfg
+        Cout, Cp, taps = w3.shape
+        Mo, n_in = table.shape[1], x.shape[0]
+        dev = x.device
+        dout = dout.float().contiguous()
+        need_x, need_w, need_res = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_res and ctx.needs_input_grad[7]
+        h2d = h2 and need_x and Cout % 32 == 0 and Mo > 0
+        dacc, gscale, dres = dout, None, None
+        if Mo and (h2d or relu or scale is not None or need_res):
+            # the epilogue's backward (ReLU mask, folded scale, residual) and, for the split-f16 dgrad, max |dacc| -> {2^k, 2^-k}
+            dacc = torch.empty(Mo, Cout, device=dev, dtype=_F32)
+            dres = torch.empty(Mo, Cout, device=dev, dtype=_F32) if need_res else None
+            gscale = torch.empty(2, device=dev, dtype=_F32) if h2d else None
+            ws = core.workspace(dev)
+            call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cout, ptr(dres),
+                 Cout, 0, None, 0, ptr(ws), ws.numel(), ptr(ag._amax_word(dev)) if h2d else None, ptr(gscale), ag.TRAIN_H2_GRAD_TARGET)
+        elif need_res:
+            dres = dout
+        dx = dw = None
+        if need_x:
+            dx = torch.zeros(n_in, Cp, device=dev, dtype=_F32)       # rows no output reads, classes without taps: zero gradient
+            if Mo and n_in:
+                src = ag._rows_h2(dacc, Cout, gscale) if h2d else dacc
+                kw = dict(h2_alpha=1.0, alpha_dev=ptr(gscale, offset=1)) if h2d else {}
+                pack = ag.pack_weights_h2_dev if h2d else ag.pack_weights_dev
+                gi, go = (1, Mo, 1, 1), (1, n_in, 1, 1)
+                if full:
+                    ag._conv_launch(src, Cout, pack(w3, Cout, Cp, taps, 3), dx, Cp, taps, gi, go, 1, 1, 0, None, None, None, False,
+                                    table=books[0], tag="sparse_hd_dgrad", **kw)
+                else:
+                    for j in range(0, len(books), 3):
+                        rows_c, taps_c, table_c = books[j:j + 3]
+                        wsub = w3.index_select(2, taps_c).contiguous()
+                        ag._conv_launch(src, Cout, pack(wsub, Cout, Cp, taps_c.numel(), 3), dx, Cp, taps_c.numel(), gi, go, 1, 1, 0, None,
+                                        None, None, False, table=table_c, tag="sparse_hd_dgrad", out_rows=rows_c, **kw)
+        if need_w:
+            dw3 = torch.zeros(Cout, Cp, taps, device=dev, dtype=_F32)
+            if Mo:
+                ws = core.workspace(dev)
+                with _lib.TIMER.region("k_wgrad<sparse hd table>", 2.0 * Mo * Cp * Cout * taps):
+                    call("coocc_conv_wgrad", ptr(x), n_in, Cp, ptr(dacc), Cout, ptr(table), Mo, Cp, Cout, taps, ptr(dw3), 0, ptr(ws),
+                         ws.numel())
+            dw = dw3[:, :Cin, :].permute(2, 1, 0).reshape(wshape).contiguous()
+        return dx, dw, None, None, None, None, None, dres, None
+
+
+def conv_bn_train(f, fh, conv, bn, table, bwd, res=None, twin=True):
+    """SparseConvV1 -> BN1d (+ res) -> ReLU on rows, differentiable: (rows, their split-f16 twin or None).  ``f`` [n_in, pad4(Cin)]
+    with its twin ``fh`` (or None), ``table`` / ``bwd`` the forward and transposed books (``SparseConvV1Fn``).  The norm follows its
+    own ``training`` flag: batch statistics (``autograd.BatchNormRowsFn``, whose apply pass writes the twin when the split-f16
+    engine will read it), or its folded running statistics in the GEMM's epilogue."""
+    from . import autograd as ag
+    if not bn.training:
+        s, b = fold_bn(bn)
+        dev = f.device
+        return SparseConvV1Fn.apply(f, conv.weight, table, bwd, fh, s.to(dev).contiguous(), b.to(dev).contiguous(), res, True), None
+    y = SparseConvV1Fn.apply(f, conv.weight, table, bwd, fh, None, None, None, False)
+    if y.shape[0] == 0:                     # no active row: nothing to normalise, no statistic to update; zero gradients
+        return y + (bn.weight.sum() + bn.bias.sum()) * 0, None
+    yh = torch.empty_like(y) if (twin and _train_h2() and y.shape[1] % 32 == 0) else None
+    return ag.BatchNormRowsFn.apply(y, bn.weight, bn.bias, res, bn, True, ag._sync_group(bn, None), yh), yh
+
+
 @MIDDLE_ENCODERS_HD.register_module()
 class SparseEncoderHD(nn.Module):
     def __init__(self, in_channels, sparse_shape, order=('conv', 'norm', 'act'), norm_cfg=dict(type='BN1d', eps=1e-3, momentum=0.01),
@@ -249,6 +422,9 @@ class SparseEncoderHD(nn.Module):
         self.conv_out = _ConvModule(cin, output_channels, (1, 1, 1), norm_cfg, stride=(1, 1, 1), padding=0)
         self._packs = PackCache(self)
         self.wide16 = WIDE16
+        # opt-in (the detectors' ``train_sparse_encoder_hd`` option sets it): under ``train()`` the forward runs the differentiable
+        # path (``forward_train_rows``); False keeps the refusal below
+        self.train_enabled = False
         self.last_active = 0                        # active outputs of the last forward
         self.last_cleared_bytes = 0                 # bytes it cleared: index maps, flag volumes, the dense volume
 
@@ -291,7 +467,7 @@ class SparseEncoderHD(nn.Module):
         """voxel_features [M, in_channels], coors [M,4] (b,z,y,x) or [M,3] (z,y,x) -> the dense [1, C, Z, Y, X] volume
         (``out.dense()``, sparse_encoder_hd.py:128-134): a zero-copy view of channels-last rows that remembers them
         (``lidar_trunk.rows_of_bczyx``), so ``lidar_trunk.run_trunk`` reads it without a transposition."""
-        if self.training:
+        if self.training and not self.train_enabled:
             raise NotImplementedError("SparseEncoderHD: the train() forward (batch-statistics BN1d, gradients through the per-axis rule "
                                       "books) is not built; call .eval()")
         if int(batch_size) != 1:
@@ -305,14 +481,17 @@ class SparseEncoderHD(nn.Module):
         if coors.shape[1] == 4:
             coors = coors[:, 1:]
         coors = coors.int().contiguous()
+        if self.training:
+            return self.forward_train_rows(voxel_features, self.rule_books(coors, transposed=True))
         levels = self.rule_books(coors)
         f = self.run_layers(voxel_features, levels)
         return self.dense_output(f, levels)
 
-    def rule_books(self, coors):
+    def rule_books(self, coors, transposed=False):
         """coors [M,3] (z,y,x) int32 -> the levels of the encoder, one per resolution in order, each with its SubM / 1x1x1 books and
-        (``.down``) the rule book of the SparseConv3d that made it.  Coordinates outside ``sparse_shape`` raise ``ValueError`` (a
-        cloud voxelised with another range, a mis-sized ``sparse_shape``): the index map is addressed by them."""
+        (``.down``) the rule book of the SparseConv3d that made it; ``transposed``: also (``.down_bwd``) that convolution's transposed
+        book for the training path (``dgrad_books``).  Coordinates outside ``sparse_shape`` raise ``ValueError`` (a cloud voxelised
+        with another range, a mis-sized ``sparse_shape``): the index map is addressed by them."""
         if coors.shape[0]:
             lo, hi = torch.stack([coors.amin(0), coors.amax(0)]).tolist()          # one host read
             if min(lo) < 0 or any(h >= n for h, n in zip(hi, self.sparse_shape)):
@@ -326,8 +505,12 @@ class SparseEncoderHD(nn.Module):
                 if isinstance(m, SparseBasicBlockHD) or m[0].subm:
                     cur.table((3, 3, 3) if isinstance(m, SparseBasicBlockHD) else m[0].kernel)
                 else:
-                    cur, tb = cur.downsample(m[0].kernel, m[0].stride, m[0].padding)
+                    prev = cur
+                    cur, tb = prev.downsample(m[0].kernel, m[0].stride, m[0].padding)
                     cur.down = tb
+                    if transposed:
+                        _, _, classes = bwd = dgrad_books(prev, cur, m[0].kernel, m[0].stride, m[0].padding)
+                        cur.down_bwd = classes if classes is not None else bwd[0]
                     levels.append(cur)
         cur.table((1, 1, 1))
         cur.dense_rows()
@@ -376,3 +559,49 @@ class SparseEncoderHD(nn.Module):
         self.last_active = cur.M
         self.last_cleared_bytes = sum(lv.cleared_bytes for lv in levels) + dense.numel() * 4
         return lt.rows_as_bczyx(Rows(dense, 1, W, H, D, C))
+
+    def forward_train_rows(self, voxel_features, levels):
+        """The differentiable forward (``train()`` with ``train_enabled``) over the levels of ``rule_books(transposed=True)`` ->
+        the same [1, C, Z, Y, X] view of channels-last rows as inference, with a ``grad_fn``.  Every BN1d follows its own
+        ``training`` flag: batch statistics over the active rows (all ranks' rows for a SyncBatchNorm a user's
+        ``convert_sync_batchnorm`` made) and running-statistics updates, or its folded running statistics in the GEMM's epilogue."""
+        from . import autograd as ag
+        from . import lidar_trunk as lt
+        M, Cin = voxel_features.shape
+        cin_p = lidar._pad4(Cin)
+        x = voxel_features.float()
+        if cin_p != Cin:
+            x = torch.cat([x, x.new_zeros(M, cin_p - Cin)], 1)
+        x = x.contiguous()
+
+        def subm_books(level, kernel):
+            tb = level.table(kernel)
+            key = ("bwd",) + tuple(kernel)
+            if key not in level.books:
+                level.books[key] = tb.flip(0).contiguous()            # the voxel at -offset: tap taps - 1 - t of the same book
+            return tb, level.books[key]
+
+        it = iter(levels)
+        cur = next(it)
+        f, fh = conv_bn_train(x, None, self.conv_input[0], self.conv_input[1], *subm_books(cur, self.conv_input[0].kernel))
+        for st in self.encoder_layers:
+            for m in st:
+                if isinstance(m, SparseBasicBlockHD):
+                    tb, tbb = subm_books(cur, (3, 3, 3))
+                    h, hh = conv_bn_train(f, fh, m.conv1, m.bn1, tb, tbb)
+                    f, fh = conv_bn_train(h, hh, m.conv2, m.bn2, tb, tbb, res=f)
+                elif m[0].subm:
+                    f, fh = conv_bn_train(f, fh, m[0], m[1], *subm_books(cur, m[0].kernel))
+                else:
+                    cur = next(it)
+                    f, fh = conv_bn_train(f, fh, m[0], m[1], cur.down, cur.down_bwd)
+        tb = cur.table((1, 1, 1))
+        f, _ = conv_bn_train(f, fh, self.conv_out[0], self.conv_out[1], tb, tb, twin=False)       # 1x1x1: one tap, its own transpose
+        D, H, W = cur.shape
+        if cur.M:
+            dense = ag.ScatterRowsFn.apply(f, cur.dense_rows(), W * H * D)
+        else:
+            dense = torch.zeros(W * H * D, self.output_channels, device=f.device, dtype=_F32) + f.sum() * 0
+        self.last_active = cur.M
+        self.last_cleared_bytes = sum(lv.cleared_bytes for lv in levels) + dense.numel() * 4
+        return lt.rows_as_bczyx(Rows(dense, 1, W, H, D, self.output_channels))

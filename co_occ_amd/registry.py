@@ -73,7 +73,7 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
     return DETECTORS.build(dict(cfg, **overrides))
 
 
-def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False):
+def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -83,9 +83,15 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     ``sparse_encoder_hd=True`` additionally replaces mmdet3d's ``SparseEncoderHD`` middle encoder (spconv v1) with
     ``lidar_hd.SparseEncoderHD``.  ``train_lidar_trunk=True`` (with ``detectors=True``: the option is the detector's) registers
     ``COOCC_Ray_L`` with its ``train_lidar_trunk`` option on by default, so an unchanged coocc_lidar.py config trains SECOND3D /
-    SECOND3DFPN on the HIP engine.  Returns False when mmdet / mmdet3d are not importable."""
+    SECOND3DFPN on the HIP engine.  ``train_sparse_encoder_hd=True`` (with ``sparse_encoder_hd=True``) registers a
+    ``SparseEncoderHD`` whose ``train_enabled`` is on, so the reference's own detector trains it under ``train()``; with
+    ``detectors=True`` our ``COOCC_Ray_L`` is registered with the option on by default as well.  Returns False when mmdet / mmdet3d
+    are not importable."""
     if train_lidar_trunk and not detectors:
         raise ValueError("register_into_mmdet: train_lidar_trunk=True is an option of this package's COOCC_Ray_L; pass detectors=True")
+    if train_sparse_encoder_hd and not sparse_encoder_hd:
+        raise ValueError("register_into_mmdet: train_sparse_encoder_hd=True trains this package's SparseEncoderHD; pass "
+                         "sparse_encoder_hd=True")
     try:
         from mmdet.models import builder as mb
         from mmdet3d.models import builder as m3b
@@ -102,18 +108,35 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     for ours, theirs in pairs:
         for k, cls in ours.module_dict.items():
             theirs.register_module(name=k, force=True, module=cls)
-    if train_lidar_trunk:
-        mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True, module=trunk_training_detector())
+    if train_sparse_encoder_hd:
+        m3b.MIDDLE_ENCODERS.register_module(name="SparseEncoderHD", force=True, module=training_sparse_encoder_hd())
+    if detectors and (train_lidar_trunk or train_sparse_encoder_hd):
+        mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True,
+                                     module=trunk_training_detector(train_lidar_trunk, train_sparse_encoder_hd))
     return True
 
 
-def trunk_training_detector():
-    """``COOCC_Ray_L`` whose ``train_lidar_trunk`` option defaults to on (what ``register_into_mmdet(train_lidar_trunk=True)`` puts
-    into mmdet's registry under the reference name)."""
+def trunk_training_detector(train_lidar_trunk=True, train_sparse_encoder_hd=False):
+    """``COOCC_Ray_L`` whose ``train_lidar_trunk`` / ``train_sparse_encoder_hd`` options default to the given values (what
+    ``register_into_mmdet(train_lidar_trunk=True)`` puts into mmdet's registry under the reference name)."""
     base = DETECTORS.get("COOCC_Ray_L")
+    trunk_default, hd_default = bool(train_lidar_trunk), bool(train_sparse_encoder_hd)
 
     class COOCC_Ray_L(base):
-        def __init__(self, *args, train_lidar_trunk=True, **kwargs):
-            super().__init__(*args, train_lidar_trunk=train_lidar_trunk, **kwargs)
+        def __init__(self, *args, train_lidar_trunk=trunk_default, train_sparse_encoder_hd=hd_default, **kwargs):
+            super().__init__(*args, train_lidar_trunk=train_lidar_trunk, train_sparse_encoder_hd=train_sparse_encoder_hd, **kwargs)
     COOCC_Ray_L.__qualname__ = "COOCC_Ray_L"
     return COOCC_Ray_L
+
+
+def training_sparse_encoder_hd():
+    """``lidar_hd.SparseEncoderHD`` with ``train_enabled`` on (what ``register_into_mmdet(train_sparse_encoder_hd=True)`` puts into
+    mmdet3d's registry: upstream's constructor signature, the differentiable forward under ``train()``)."""
+    from . import lidar_hd
+
+    class SparseEncoderHD(lidar_hd.SparseEncoderHD):
+        def __init__(self, *args, **kwargs):
+            super().__init__(*args, **kwargs)
+            self.train_enabled = True
+    SparseEncoderHD.__qualname__ = "SparseEncoderHD"
+    return SparseEncoderHD

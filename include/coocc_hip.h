@@ -861,6 +861,21 @@ int coocc_conv_tap_table3(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo,
 int coocc_fpn_sum_bwd(const float* dout, int dout_stride, float* const* dups, const int* strides, int levels, int B, int X, int Y,
                       int Z, int C, void* stream);
 
+/* ---- training of SparseEncoderHD (co_occ_amd/lidar_hd.py, csrc/sparse_train.hip) */
+/* The TRANSPOSED rule book of a per-axis SparseConv3d (conventions of coocc_sparse_conv_table3): table[t][i] = the output row that
+ * reads input row i through tap t = (kd*ky + kh)*kx + kw, i.e. the row of ((z + pz - kd) / sz, ...) in `out_map` (the index map of
+ * the OUTPUT level, [Do*Ho*Wo], coocc_sparse_index_map) when every axis divides and lies in range, else -1.  table:[kz*ky*kx][Mi],
+ * every entry written once.  classes (optional, [Mi]): the residue class ((z+pz) % sz * sy + (y+py) % sy) * sx + (x+px) % sx of every
+ * input row, written by the same launch; a row of class (rz,ry,rx) is reached only through taps with kd % sz == rz, kh % sy == ry,
+ * kw % sx == rx.  (Do,Ho,Wo) is checked against (in + 2p - k)/s + 1 per axis. */
+int coocc_sparse_dgrad_table3(const int32_t* in_coors, int Mi, int Di, int Hi, int Wi, int kz, int ky, int kx, int sz, int sy, int sx,
+                              int pz, int py, int px, int Do, int Ho, int Wo, const int32_t* out_map, int32_t* table, int32_t* classes,
+                              void* stream);
+/* coocc_bn_apply (the same fp32 bits in y) whose pass also writes the split-f16 twin of y, H2 rows [M][C] (C % 32 == 0), the bytes
+ * coocc_rows_to_h2 makes from y; out_h2 NULL = none.  C % 4 == 0, 16-byte aligned pointers. */
+int coocc_bn_apply_ex(const float* x, int M, int C, const float* mean, const float* var, const float* gamma, const float* beta,
+                      float eps, const float* res, int relu, float* y, void* out_h2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

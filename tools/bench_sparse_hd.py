@@ -10,7 +10,16 @@ ms per sample of the encoder (HIP events around ``calls`` calls after ``warmup``
 its pieces, each timed on its own in the same way: the GEMM launches up to ``conv_out`` over prebuilt rule books
 (``SparseEncoderHD.run_layers``) and the dense write (the volume's clear + ``conv_out``'s scattering GEMM, ``dense_output``).  The rule
 books (index maps, flags, compaction, tables; ``rule_books``, with the bytes cleared per sample and its three host reads) and
-voxelise + VFE do not depend on the engine and are timed once.  Prints one JSON line."""
+voxelise + VFE do not depend on the engine and are timed once.  Prints one JSON line.
+
+    python tools/bench_sparse_hd.py --train [--out profiles/sparse_hd_train_bench.json]
+
+``--train``: one forward + backward of the module under ``train()`` (``train_enabled``) on the same cloud, timed the same way, for
+COOCC_HD_TRAIN_H2 1 / 0 (split-f16 against fp32-MFMA rule-book GEMMs) x COOCC_HD_DGRAD_CLASSES 1 / 0 (the strided dgrad per residue
+class against one 27-tap launch over the full transposed book); and on their own: the transposed books of the three
+down-convolutions from ``coocc_sparse_dgrad_table3`` (with and without the class lists' sort, host read and gathers) against
+``lidar._inverse_table`` on the same forward books, and a training-mode BN1d forward per level with the split-f16 twin written by
+its apply pass (``coocc_bn_apply_ex``) against the apply pass followed by ``coocc_rows_to_h2``."""
 import argparse
 import json
 import os
@@ -29,6 +38,7 @@ def main():
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--points", type=int, default=400000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--train", action="store_true", help="time the training step (forward + backward) instead of inference")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_sparse_hd needs the MI355X: there is no CPU fallback")
@@ -61,6 +71,19 @@ def main():
         torch.cuda.synchronize()
         v = sorted(window(fn) for _ in range(a.windows))
         return dict(median_ms=round(v[len(v) // 2], 4), min_ms=round(v[0], 4), max_ms=round(v[-1], 4))
+
+    if a.train:
+        with torch.no_grad():
+            voxels, coors, num = vl(pts)
+            feats = vfe(voxels, num, coors)
+        res = train_bench(a, m, feats, coors, timed)
+        core.check_h2_overflow()
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
 
     with torch.no_grad():
         def producer():
@@ -100,6 +123,63 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
+
+
+def train_bench(a, m, feats, coors, timed):
+    from co_occ_amd import autograd as ag, core, lidar, lidar_hd
+    from co_occ_amd._lib import call, ptr
+    dev = feats.device
+    m.train()
+    m.train_enabled = True
+    gout = torch.randn(1, m.output_channels, *m.out_shape(), device=dev)
+
+    def step():
+        m.zero_grad(set_to_none=True)
+        (m(feats, coors, 1) * gout).sum().backward()
+
+    def forward_only():
+        with torch.no_grad():
+            m(feats, coors, 1)
+    levels = m.rule_books(coors, transposed=True)
+    res = dict(workload="coocc_lidar SparseEncoderHD [65,800,800] under train(), %d voxels" % coors.shape[0], calls=a.calls, warmup=a.warmup,
+               windows=a.windows, active_per_level=[lv.M for lv in levels], step={}, transposed_books=[], bn_forward=[])
+    old = core.CONV_ENGINE, lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES
+    core.CONV_ENGINE = "h2"
+    for h2 in (1, 0):
+        for classes in (1, 0):
+            lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES = bool(h2), bool(classes)
+            res["step"]["train_h2=%d dgrad_classes=%d" % (h2, classes)] = dict(forward_backward=timed(step), forward=timed(forward_only))
+    core.CONV_ENGINE, lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES = old
+    # the transposed book of every down-convolution: the device kernel from geometry (alone, and with the class lists) against the
+    # boolean-mask construction of lidar._inverse_table on the same forward book
+    downs = [mod[0] for st in m.encoder_layers for mod in st if isinstance(mod, lidar_hd._ConvModule) and not mod[0].subm]
+    for conv, lo, hi in zip(downs, levels[:-1], levels[1:]):
+        k, s, p = conv.kernel, conv.stride, conv.padding
+        got = lidar_hd.dgrad_books(lo, hi, k, s, p, by_class=False)[0]
+        assert torch.equal(got, lidar._inverse_table(hi.down, lo.M)), "the two constructions disagree"
+        res["transposed_books"].append(dict(
+            rows_in=lo.M, rows_out=hi.M, stride=list(s), padding=list(p),
+            dgrad_table3=timed(lambda: lidar_hd.dgrad_books(lo, hi, k, s, p, by_class=False)),
+            dgrad_table3_with_class_lists=timed(lambda: lidar_hd.dgrad_books(lo, hi, k, s, p, by_class=True)),
+            inverse_table_torch=timed(lambda: lidar._inverse_table(hi.down, lo.M))))
+    # a training-mode BN1d forward (statistics + apply) per level at that level's width
+    for lv, C in zip(levels, [m.base_channels] + [conv.cout for conv in downs]):
+        if C % 32 or not lv.M:
+            continue
+        x = torch.randn(lv.M, C, device=dev)
+        bn = torch.nn.BatchNorm1d(C, eps=1e-3, momentum=0.01).to(dev).train()
+        twin = torch.empty_like(x)
+
+        def fused():
+            with torch.no_grad():
+                ag.BatchNormRowsFn.apply(x, bn.weight, bn.bias, None, bn, True, None, twin)
+
+        def separate():
+            with torch.no_grad():
+                y = ag.BatchNormRowsFn.apply(x, bn.weight, bn.bias, None, bn, True, None)
+                call("coocc_rows_to_h2", ptr(y), C, lv.M, C, 1.0, ptr(twin))
+        res["bn_forward"].append(dict(rows=lv.M, C=C, fused_twin=timed(fused), apply_then_rows_to_h2=timed(separate)))
+    return res
 
 
 if __name__ == "__main__":
