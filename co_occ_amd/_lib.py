@@ -137,6 +137,7 @@ SIGNATURES = {
     "coocc_conv_epilogue_bwd": (I, [P, I, P, I, P, I, I, I, P, I, P, I, I, P, I, P, L, P]),
     "coocc_conv_epilogue_bwd_ex": (I, [P, I, P, I, P, I, I, I, P, I, P, I, I, P, I, P, L, P, P, F, P]),
     "coocc_conv_wgrad": (I, [P, I, I, P, I, P, I, I, I, I, P, I, P, L, P]),
+    "coocc_conv_wgrad_h2t": (I, [P, I, I, P, I, P, I, I, I, I, P, P, I, P, L, P]),
     "coocc_gather_rows": (I, [P, I, P, I, I, P, I, P]),
     "coocc_scatter_add_rows": (I, [P, I, P, I, I, P, I, P]),
     "coocc_voxel_pool_bwd": (I, [P, I, P, I, I, I, P, I, I, I, I, P, P]),

@@ -207,7 +207,8 @@ class SparseBasicBlockHD(nn.Module):
 #   dgrad    dx[i] = sum_t W_t . dy[bwd[t][i]]                   the same GEMM over the TRANSPOSED book.  SubMConv3d: table.flip(0) (the
 #                                                                active set is its own mirror image); SparseConv3d:
 #                                                                coocc_sparse_dgrad_table3, made on the device from geometry
-#   wgrad    dW_t  = sum_o x[table[t][o]] (x) dy[o]              coocc_conv_wgrad with the forward book (fp32 MFMA on every engine)
+#   wgrad    dW_t  = sum_o x[table[t][o]] (x) dy[o]              coocc_conv_wgrad with the forward book (fp32 MFMA), or, opt-in,
+#                                                                coocc_conv_wgrad_h2t (split-f16, COOCC_HD_WGRAD_H2 below)
 # BN1d = ``autograd.BatchNormRowsFn`` on the active rows (batch statistics, running-statistics updates, residual + ReLU inside); its
 # apply pass writes the split-f16 twin the next GEMM reads (coocc_bn_apply_ex).  conv_out's rows reach the dense volume through
 # ``autograd.ScatterRowsFn``.  The 16-wide first stage trains on 16-wide rows on the fp32-MFMA kernels (no zero-padded columns in
@@ -216,8 +217,15 @@ class SparseBasicBlockHD(nn.Module):
 # kernels when COOCC_CONV_ENGINE=h2, COOCC_LIDAR_H2=1 and COOCC_TRAIN_H2=1 (packs made on the device every step, the gradient operand
 # scaled by the device-chosen power of two of autograd.TRAIN_H2_DGRAD); 0 = fp32 MFMA everywhere.  MEASURED at the config's size
 # (120 000 voxels on [65,800,800], forward + backward, profiles/sparse_hd_train_bench.json): 57.3 ms against 66.0 ms, the forward
-# alone 5.1 against 9.2 ms.  Weight gradients are coocc_conv_wgrad (fp32 MFMA) either way and are most of the rest.
+# alone 5.1 against 9.2 ms.  Weight gradients are coocc_conv_wgrad (fp32 MFMA) either way and are most of the rest, unless:
+# COOCC_HD_WGRAD_H2 (default 0): under the conditions above, the weight gradient of a layer with pad4(Cin) % 32 == 0 and Cout % 32
+# == 0 runs on the split-f16 row-table kernel coocc_conv_wgrad_h2t (csrc/wgrad_h2t.hip: operands gathered and split in registers,
+# 32-channel x 32/64-output tiles per wave, the gradient operand scaled by the dgrad's device-chosen power of two) instead of the
+# fp32 MFMA's 128 x 128 tiles.  conv_input, the 16-wide stage and COOCC_CONV_ENGINE=f32 keep coocc_conv_wgrad.  MEASURED, same
+# size (profiles/sparse_hd_wgrad_bench.json, tools/bench_sparse_hd.py --train; per shape in DESIGN.md 8): 1.05-3.2x per layer
+# shape, none slower; forward + backward 36.3 ms with 1 against 58.0 ms with 0.  The default stays 0 until a change of its own.
 HD_TRAIN_H2 = os.environ.get("COOCC_HD_TRAIN_H2", "1") != "0"
+HD_WGRAD_H2 = os.environ.get("COOCC_HD_WGRAD_H2", "0") != "0"
 # 1: the dgrad of a strided SparseConv3d runs as one row-table GEMM per residue class of the input rows over that class's live taps
 # (1, 2, 4 or 8 of 27 at stride 2); 0: one launch over all taps of the full transposed book (7/8 of whose entries are -1 at stride
 # 2).  Same values up to summation order.  MEASURED, same run: the backward takes 52.2 ms either way -- the row-table kernels skip
@@ -316,15 +324,17 @@ class SparseConvV1Fn(torch.autograd.Function):
         dout = dout.float().contiguous()
         need_x, need_w, need_res = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_res and ctx.needs_input_grad[7]
         h2d = h2 and need_x and Cout % 32 == 0 and Mo > 0
+        h2w = HD_WGRAD_H2 and h2 and need_w and Cp % 32 == 0 and Cout % 32 == 0 and Mo > 0
+        h2g = h2d or h2w                                            # a split-f16 GEMM reads dacc: it needs the gradient scale
         dacc, gscale, dres = dout, None, None
-        if Mo and (h2d or relu or scale is not None or need_res):
-            # the epilogue's backward (ReLU mask, folded scale, residual) and, for the split-f16 dgrad, max |dacc| -> {2^k, 2^-k}
+        if Mo and (h2g or relu or scale is not None or need_res):
+            # the epilogue's backward (ReLU mask, folded scale, residual) and, for the split-f16 dgrad / wgrad, max |dacc| -> {2^k, 2^-k}
             dacc = torch.empty(Mo, Cout, device=dev, dtype=_F32)
             dres = torch.empty(Mo, Cout, device=dev, dtype=_F32) if need_res else None
-            gscale = torch.empty(2, device=dev, dtype=_F32) if h2d else None
+            gscale = torch.empty(2, device=dev, dtype=_F32) if h2g else None
             ws = core.workspace(dev)
             call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cout, ptr(dres),
-                 Cout, 0, None, 0, ptr(ws), ws.numel(), ptr(ag._amax_word(dev)) if h2d else None, ptr(gscale), ag.TRAIN_H2_GRAD_TARGET)
+                 Cout, 0, None, 0, ptr(ws), ws.numel(), ptr(ag._amax_word(dev)) if h2g else None, ptr(gscale), ag.TRAIN_H2_GRAD_TARGET)
         elif need_res:
             dres = dout
         dx = dw = None
@@ -348,9 +358,14 @@ class SparseConvV1Fn(torch.autograd.Function):
             dw3 = torch.zeros(Cout, Cp, taps, device=dev, dtype=_F32)
             if Mo:
                 ws = core.workspace(dev)
-                with _lib.TIMER.region("k_wgrad<sparse hd table>", 2.0 * Mo * Cp * Cout * taps):
-                    call("coocc_conv_wgrad", ptr(x), n_in, Cp, ptr(dacc), Cout, ptr(table), Mo, Cp, Cout, taps, ptr(dw3), 0, ptr(ws),
-                         ws.numel())
+                if h2w:
+                    with _lib.TIMER.region("k_wgrad_h2t<sparse hd table>", 2.0 * Mo * Cp * Cout * taps):
+                        call("coocc_conv_wgrad_h2t", ptr(x), n_in, Cp, ptr(dacc), Cout, ptr(table), Mo, Cp, Cout, taps, ptr(gscale),
+                             ptr(dw3), 0, ptr(ws), ws.numel())
+                else:
+                    with _lib.TIMER.region("k_wgrad<sparse hd table>", 2.0 * Mo * Cp * Cout * taps):
+                        call("coocc_conv_wgrad", ptr(x), n_in, Cp, ptr(dacc), Cout, ptr(table), Mo, Cp, Cout, taps, ptr(dw3), 0, ptr(ws),
+                             ws.numel())
             dw = dw3[:, :Cin, :].permute(2, 1, 0).reshape(wshape).contiguous()
         return dx, dw, None, None, None, None, None, dres, None
 

@@ -424,6 +424,18 @@ int coocc_conv_epilogue_bwd_ex(const float* dout, int dout_stride, const float* 
 int coocc_conv_wgrad(const float* in, int in_rows, int in_stride, const float* dacc, int dacc_stride,
                      const int32_t* table, int M, int Cin, int Cout, int taps, float* dw, int accumulate,
                      float* ws, int64_t ws_floats, void* stream);
+/* dw[Cout][Cin][taps] (=|+=) sum_m in[table[t][m]][c] * dacc[m][n]   (table entry -1: the row contributes nothing)
+ * on the split-f16 engine: both fp32 operands split in registers (hi = f16(v), lo = f16((v - hi) 2^11)), three
+ * v_mfma_f32_32x32x16_f16 per product (hi hi, hi lo, lo hi), fp32 accumulate; the voxel index is K.
+ * scale2: NULL, or the device pair {s, 1/s} of coocc_conv_epilogue_bwd_ex -- dacc is multiplied by s before the split,
+ * the accumulators by 1/s.  Cin % 32 == 0, Cout % 32 == 0, table required.  Same dw layout, workspace contract,
+ * 4 GB operand limit and deterministic slice-order reduction as coocc_conv_wgrad.  (csrc/wgrad_h2t.hip; the weight
+ * gradient spconv v1's fp32 backward gives the SubMConv3d / SparseConv3d layers of sparse_encoder_hd.py:66-212,
+ * which torch.autograd reaches through spconv's own CUDA ops upstream.)  Values at or above the 16-bit operand
+ * guard (or NaN) in `in` or in dacc * s raise the flag of coocc_h2_overflow. */
+int coocc_conv_wgrad_h2t(const float* in, int in_rows, int in_stride, const float* dacc, int dacc_stride,
+                         const int32_t* table, int M, int Cin, int Cout, int taps, const float* scale2,
+                         float* dw, int accumulate, float* ws, int64_t ws_floats, void* stream);
 
 /* ---- backward of the HBM-bound ops (torch autograd over eager index_put / cumprod / interpolate upstream) */
 /* dst[r] = src[idx[r]] (zeros for idx < 0) and its adjoint dst[idx[r]] += src[r] (fp32 atomics): the G1 row

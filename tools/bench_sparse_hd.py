@@ -19,7 +19,12 @@ COOCC_HD_TRAIN_H2 1 / 0 (split-f16 against fp32-MFMA rule-book GEMMs) x COOCC_HD
 class against one 27-tap launch over the full transposed book); and on their own: the transposed books of the three
 down-convolutions from ``coocc_sparse_dgrad_table3`` (with and without the class lists' sort, host read and gathers) against
 ``lidar._inverse_table`` on the same forward books, and a training-mode BN1d forward per level with the split-f16 twin written by
-its apply pass (``coocc_bn_apply_ex``) against the apply pass followed by ``coocc_rows_to_h2``."""
+its apply pass (``coocc_bn_apply_ex``) against the apply pass followed by ``coocc_rows_to_h2``.  ``wgrad``: per distinct layer shape
+that qualifies for the split-f16 rule-book weight gradient (pad4(Cin) % 32 == 0, Cout % 32 == 0), ``coocc_conv_wgrad`` (fp32 MFMA)
+against ``coocc_conv_wgrad_h2t`` on the same operands and the level's own book, in alternating windows, with the share of the f16
+MFMA peak (the three split products of every live book entry over 2.5 PFLOP/s) and of the HBM peak (live entries x row bytes +
+dacc + the slabs written and read back, over 8 TB/s) the new kernel reaches; and the step with COOCC_HD_WGRAD_H2=1 beside the same
+step with 0 in the same alternating windows (``--out profiles/sparse_hd_wgrad_bench.json``)."""
 import argparse
 import json
 import os
@@ -72,11 +77,24 @@ def main():
         v = sorted(window(fn) for _ in range(a.windows))
         return dict(median_ms=round(v[len(v) // 2], 4), min_ms=round(v[0], 4), max_ms=round(v[-1], 4))
 
+    def timed_alternating(fns):
+        """``timed`` for several functions at once: one window of each in turn, ``windows`` times over."""
+        for fn in fns:
+            for _ in range(a.warmup):
+                fn()
+        torch.cuda.synchronize()
+        v = [[] for _ in fns]
+        for _ in range(a.windows):
+            for i, fn in enumerate(fns):
+                v[i].append(window(fn))
+        v = [sorted(w) for w in v]
+        return [dict(median_ms=round(w[len(w) // 2], 4), min_ms=round(w[0], 4), max_ms=round(w[-1], 4)) for w in v]
+
     if a.train:
         with torch.no_grad():
             voxels, coors, num = vl(pts)
             feats = vfe(voxels, num, coors)
-        res = train_bench(a, m, feats, coors, timed)
+        res = train_bench(a, m, feats, coors, timed, timed_alternating)
         core.check_h2_overflow()
         line = json.dumps(res)
         print(line)
@@ -125,7 +143,79 @@ def main():
             f.write(line + "\n")
 
 
-def train_bench(a, m, feats, coors, timed):
+F16_MFMA_PEAK, HBM_PEAK = 2.5e15, 8.0e12          # MI355X: dense f16 MFMA FLOP/s, HBM3E bytes/s (both spec)
+
+
+def hd_layers(m, levels):
+    """(SparseConvV1, its forward book [taps, rows out], rows in) of every convolution of the module, in forward order."""
+    from co_occ_amd import lidar_hd
+    it = iter(levels)
+    cur = next(it)
+    out = [(m.conv_input[0], cur.table(m.conv_input[0].kernel), cur.M)]
+    for st in m.encoder_layers:
+        for mod in st:
+            if isinstance(mod, lidar_hd.SparseBasicBlockHD):
+                out += [(mod.conv1, cur.table((3, 3, 3)), cur.M), (mod.conv2, cur.table((3, 3, 3)), cur.M)]
+            elif mod[0].subm:
+                out.append((mod[0], cur.table(mod[0].kernel), cur.M))
+            else:
+                n_in = cur.M
+                cur = next(it)
+                out.append((mod[0], cur.down, n_in))
+    out.append((m.conv_out[0], cur.table((1, 1, 1)), cur.M))
+    return out
+
+
+def h2t_slices(Mo, Cin, Cout, taps, ws_floats):
+    """The row slices coocc_conv_wgrad_h2t cuts (csrc/wgrad_h2t.hip): what its slabs cost in bytes."""
+    items = (taps + 1) // 2 * (Cin // 32) * (Cout // 64) if Cout % 64 == 0 else (taps + 2) // 3 * (Cin // 32) * (Cout // 32)
+    wgs = (items + 3) // 4
+    n = min((512 + wgs - 1) // wgs, (Mo + 255) // 256, ws_floats // (taps * Cin * Cout), 4096)
+    mslice = ((Mo + n - 1) // n + 15) // 16 * 16
+    return (Mo + mslice - 1) // mslice
+
+
+def wgrad_bench(m, levels, timed_alternating):
+    from co_occ_amd import core, lidar
+    from co_occ_amd._lib import call, ptr
+    recs, seen = [], {}
+    for conv, table, n_in in hd_layers(m, levels):
+        taps, Mo = table.shape
+        Cp, Cout = lidar._pad4(conv.cin), conv.cout
+        key = (Mo, n_in, Cp, Cout, taps)
+        if Cp % 32 or Cout % 32 or not Mo:
+            continue
+        if key in seen:
+            seen[key]["layers"] += 1
+            continue
+        dev = table.device
+        x, dacc = torch.randn(n_in, Cp, device=dev), torch.randn(Mo, Cout, device=dev)
+        one = torch.ones(2, device=dev)
+        dw_a, dw_b = torch.empty(Cout, Cp, taps, device=dev), torch.empty(Cout, Cp, taps, device=dev)
+        ws = core.workspace(dev)
+
+        def f32():
+            call("coocc_conv_wgrad", ptr(x), n_in, Cp, ptr(dacc), Cout, ptr(table), Mo, Cp, Cout, taps, ptr(dw_a), 0, ptr(ws), ws.numel())
+
+        def h2t():
+            call("coocc_conv_wgrad_h2t", ptr(x), n_in, Cp, ptr(dacc), Cout, ptr(table), Mo, Cp, Cout, taps, ptr(one), ptr(dw_b), 0, ptr(ws),
+                 ws.numel())
+        t32, th = timed_alternating([f32, h2t])
+        live = int((table >= 0).sum())
+        nsl = h2t_slices(Mo, Cp, Cout, taps, ws.numel())
+        nbytes = live * Cp * 4 + Mo * Cout * 4 + 2 * nsl * taps * Cp * Cout * 4
+        sec = th["median_ms"] * 1e-3
+        rec = dict(rows_out=Mo, rows_in=n_in, Cin=Cp, Cout=Cout, taps=taps, layers=1, live_share=round(live / (taps * Mo), 4),
+                   coocc_conv_wgrad=t32, coocc_conv_wgrad_h2t=th, speedup=round(t32["median_ms"] / th["median_ms"], 3),
+                   slices=nsl, f16_mfma_peak_fraction=round(3 * 2.0 * live * Cp * Cout / sec / F16_MFMA_PEAK, 5),
+                   hbm_peak_fraction=round(nbytes / sec / HBM_PEAK, 4), bytes=nbytes,
+                   max_diff_rel=float((dw_a - dw_b).abs().max() / dw_a.abs().max().clamp_min(1e-30)))
+        seen[key] = rec
+        recs.append(rec)
+    return recs
+
+
+def train_bench(a, m, feats, coors, timed, timed_alternating):
     from co_occ_amd import autograd as ag, core, lidar, lidar_hd
     from co_occ_amd._lib import call, ptr
     dev = feats.device
@@ -143,13 +233,24 @@ def train_bench(a, m, feats, coors, timed):
     levels = m.rule_books(coors, transposed=True)
     res = dict(workload="coocc_lidar SparseEncoderHD [65,800,800] under train(), %d voxels" % coors.shape[0], calls=a.calls, warmup=a.warmup,
                windows=a.windows, active_per_level=[lv.M for lv in levels], step={}, transposed_books=[], bn_forward=[])
-    old = core.CONV_ENGINE, lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES
-    core.CONV_ENGINE = "h2"
+    old = core.CONV_ENGINE, lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES, lidar_hd.HD_WGRAD_H2
+    core.CONV_ENGINE, lidar_hd.HD_WGRAD_H2 = "h2", False
     for h2 in (1, 0):
         for classes in (1, 0):
             lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES = bool(h2), bool(classes)
             res["step"]["train_h2=%d dgrad_classes=%d" % (h2, classes)] = dict(forward_backward=timed(step), forward=timed(forward_only))
-    core.CONV_ENGINE, lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES = old
+    # the split-f16 rule-book weight gradient: the step with the knob on and off in the same alternating windows
+    lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES = True, False
+
+    def step_knob(on):
+        def fn():
+            lidar_hd.HD_WGRAD_H2 = on
+            step()
+        return fn
+    t_on, t_off = timed_alternating([step_knob(True), step_knob(False)])
+    res["step"]["train_h2=1 dgrad_classes=0 wgrad_h2=1"] = dict(forward_backward=t_on, forward_backward_wgrad_h2_0_same_windows=t_off)
+    core.CONV_ENGINE, lidar_hd.HD_TRAIN_H2, lidar_hd.HD_DGRAD_CLASSES, lidar_hd.HD_WGRAD_H2 = old
+    res["wgrad"] = wgrad_bench(m, levels, timed_alternating)
     # the transposed book of every down-convolution: the device kernel from geometry (alone, and with the class lists) against the
     # boolean-mask construction of lidar._inverse_table on the same forward book
     downs = [mod[0] for st in m.encoder_layers for mod in st if isinstance(mod, lidar_hd._ConvModule) and not mod[0].subm]
