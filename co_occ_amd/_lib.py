@@ -185,6 +185,10 @@ SIGNATURES = {
     "coocc_render_panels": (I, [P, P, P, P, I, I, I, P, P]),
     "coocc_sparse_dgrad_table3": (I, [P] + [I] * 16 + [P, P, P, P]),
     "coocc_bn_apply_ex": (I, [P, I, I, P, P, P, P, F, P, I, P, P, P]),
+    "coocc_pool_labels": (I, [P, I, I, I, I, I, I, I, P, P]),
+    "coocc_occ_loss_ws": (Z, [L, I]),
+    "coocc_occ_loss_fwd": (I, [P, L, I, I, P, P, I, I, I, P, P, I, P, P, P, P, Z, P]),
+    "coocc_occ_loss_bwd": (I, [P, L, I, I, P, P, I, P, P, P, P, I, P]),
 }
 
 _lib = None

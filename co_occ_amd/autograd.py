@@ -610,6 +610,40 @@ class RenderLossesFn(torch.autograd.Function):
         return drgbs, ddepths, None, None, None
 
 
+class OccLossFn(torch.autograd.Function):
+    """-> tensor [4] = the unweighted (ce, sem_scal, geo_scal, lovasz) of OccHead.loss (co_occ_amd/losses.py) for logit rows [P,C]
+    (unit column stride, row stride ld >= C, read in place).  ``labels``: uint8 [P], or with ``coords`` ([3,P] int64) the label volume
+    [X,Y,Z] read at the coordinates.  The backward is ONE coocc_occ_loss_bwd call on the saved statistics and Lovasz weights."""
+
+    @staticmethod
+    def forward(ctx, rows, labels, coords, class_w, empty_idx):
+        P, C = rows.shape
+        ld = rows.stride(0) if P > 1 else C
+        dev = rows.device
+        out = torch.empty(4, device=dev, dtype=_F32)
+        stats = torch.empty(208, device=dev, dtype=torch.float64)          # COOCC_OCC_LOSS_STATS
+        lov_w = torch.empty(P, C, device=dev, dtype=_F32)
+        ws = stream_buffer(dev, "s:occ_loss", (int(_lib.load().coocc_occ_loss_ws(P, C)) + 3) // 4)
+        if coords is not None:
+            row_labels, (VX, VY, VZ) = torch.empty(P, device=dev, dtype=torch.uint8), labels.shape
+        else:
+            row_labels, VX, VY, VZ = None, 0, 0, 0
+        call("coocc_occ_loss_fwd", ptr(rows, _F32, strided=True), P, C, ld, ptr(labels, torch.uint8), ptr(coords, torch.int64), VX, VY, VZ,
+             ptr(row_labels), ptr(class_w, _F32), int(empty_idx), ptr(out), ptr(stats), ptr(lov_w), ptr(ws), ws.numel() * 4)
+        ctx.save_for_backward(rows, labels if row_labels is None else row_labels, class_w, stats, lov_w)
+        ctx.cfg = (P, C, ld, int(empty_idx))
+        return out
+
+    @staticmethod
+    def backward(ctx, gl):
+        rows, row_labels, class_w, stats, lov_w = ctx.saved_tensors
+        P, C, ld, empty_idx = ctx.cfg
+        drows = torch.empty(P, C, device=rows.device, dtype=_F32)
+        call("coocc_occ_loss_bwd", ptr(rows, _F32, strided=True), P, C, ld, ptr(row_labels), ptr(class_w), empty_idx, ptr(stats),
+             ptr(lov_w), ptr(gl.float().contiguous()), ptr(drows), C)
+        return drows, None, None, None, None
+
+
 def render_block_train(sigma_head, rgb_head, feats2d, grid, gemo, scale=16):
     """Differentiable render block: feats2d [X*Y*Z, C] rows -> (rgbs, depths).  The per-voxel heads run through
     ConvRowsFn (Linear+ReLU layers), so gradients reach the voxel features and both MLPs.  ``rgb_head=None``: the

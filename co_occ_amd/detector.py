@@ -104,7 +104,7 @@ class COOCC_Ray(nn.Module):
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
-                 train_lidar_trunk=False, train_sparse_encoder_hd=False, **kwargs):
+                 train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -161,6 +161,11 @@ class COOCC_Ray(nn.Module):
         self.graph_unavailable = None               # why simple_test fell back to the eager path, if it did
         self.img_view_transformer = registry.build_neck(img_view_transformer) if img_view_transformer else None
         self.pts_bbox_head = registry.build_head(pts_bbox_head) if pts_bbox_head else None
+        # opt-in: OccHead.loss computes its eight voxel / fine-point terms and their gradient on the device (losses.occ_loss_terms_device:
+        # no host read, bitwise reproducible) instead of eager torch
+        self.device_occ_losses = bool(device_occ_losses)
+        if self.pts_bbox_head is not None:
+            self.pts_bbox_head.device_losses = self.device_occ_losses
         self.occ_fuser = registry.build_fusion_layer(occ_fuser) if occ_fuser is not None else None
         self.semantic_encoder = registry.build_backbone(semantic_encoder)
         self.semantic_neck = registry.build_neck(semantic_neck)

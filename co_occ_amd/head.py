@@ -86,6 +86,9 @@ class OccHead(nn.Module):
         from .losses import nusc_class_weights
         self.class_weights = nusc_class_weights() if balance_cls_weight else torch.ones(17) / 17     # :134-144
         self.visible_loss = visible_loss
+        # opt-in: loss_voxel / loss_point compute their four terms and the gradient on the device (losses.occ_loss_terms_device /
+        # pool_labels_device: no host read, bitwise reproducible) instead of eager torch; same keys, same weights
+        self.device_losses = False
 
         if cascade_ratio != 1 and (sample_from_voxel or sample_from_img):
             fine_in = 128 if sample_from_voxel else 0
@@ -566,15 +569,33 @@ class OccHead(nn.Module):
             'loss_voxel_lovasz_%s' % tag: self.loss_voxel_lovasz_weight * L.lovasz_softmax(torch.softmax(logits, dim=1), target,
                                                                                            ignore=255)}
 
+    def _loss_terms_device(self, terms, tag):
+        w = (self.loss_voxel_ce_weight, self.loss_voxel_sem_scal_weight, self.loss_voxel_geo_scal_weight, self.loss_voxel_lovasz_weight)
+        return {'loss_voxel_%s_%s' % (n, tag): w[i] * terms[i] for i, n in enumerate(("ce", "sem_scal", "geo_scal", "lovasz"))}
+
+    def _class_weights_on(self, device):
+        cw = getattr(self, "_cw_dev", None)
+        if cw is None or cw[0] is not self.class_weights or cw[1].device != device:      # one upload per device, not one per step
+            cw = self._cw_dev = (self.class_weights, self.class_weights.to(device=device, dtype=torch.float32))
+        return cw[1]
+
     def loss_voxel(self, output_voxels, target_voxels, tag):
         """occ_head.py:265-293: labels majority-pooled to the logits' grid, then the four terms (class-weighted CE)."""
         from .losses import pool_labels
         B, C, H, W, D = output_voxels.shape
+        if self.device_losses:
+            from . import losses as L
+            target = L.pool_labels_device(target_voxels, H, W, D, self.empty_idx, num_cls=self.out_channel, dtype=torch.uint8)
+            return self._loss_terms_device(L.occ_loss_terms_device(output_voxels, target, self._class_weights_on(output_voxels.device),
+                                                                   self.empty_idx), tag)
         target = pool_labels(target_voxels, H, W, D, self.empty_idx, num_cls=self.out_channel)
         return self._loss_terms(output_voxels, target, tag, self.class_weights.to(output_voxels))
 
     def loss_point(self, fine_coord, fine_output, target_voxels, tag):
         """occ_head.py:295-310: fine logits [N,ncls] against the labels at their coordinates (unweighted CE)."""
+        if self.device_losses:
+            from . import losses as L
+            return self._loss_terms_device(L.occ_loss_terms_device(fine_output, target_voxels, None, self.empty_idx, coords=fine_coord), tag)
         gt = target_voxels[:, fine_coord[0, :], fine_coord[1, :], fine_coord[2, :]].long()[0]
         return self._loss_terms(fine_output, gt, tag, None)
 

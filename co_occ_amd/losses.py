@@ -2,8 +2,10 @@
 semantic / geometric scene-class affinity losses (P/utils/semkitti.py:65-149) and Lovasz-softmax
 (P/coocc/dense_heads/lovasz_softmax.py:156-203), plus the majority-vote label pooling of ``loss_voxel`` (:269-281).
 
-Host-side eager torch on the logits the HIP path produced, exactly as upstream (the losses are a few reductions over
-80 k coarse voxels / <= 8 x fine_topk fine points; they are downstream of the hot path).  Restated in
+The functions below are host-side eager torch on the logits the HIP path produced, exactly as upstream; ``occ_loss_terms_device`` /
+``pool_labels_device`` at the end of the file compute the same numbers and their gradient in HIP kernels (csrc/occ_loss.hip, opt-in
+through ``OccHead.device_losses``).  (The losses are a few reductions over
+80 k coarse voxels / <= 8 x fine_topk fine points; they are downstream of the hot path)  Restated in
 vectorised form -- one softmax, one one-hot matmul for all per-class sums, one column-wise sort for all present classes
 -- instead of the reference's per-class Python loops; the arithmetic (sums, ratios, -log clamped at 100) is the same, so
 values agree to float rounding (tests/golden/losses.npz, generated from the unmodified reference functions)."""
@@ -126,3 +128,68 @@ def pool_labels(target_voxels, H, W, D, empty_idx=0, num_cls=17):
     arg = torch.where(arg == num_cls, torch.full_like(arg, 255), arg)
     out = torch.where((m == 1) & (n_empty > 0), torch.full_like(arg, 255), arg)
     return torch.where(all_empty, torch.full_like(arg, empty_idx), out).long()
+
+
+# ----------------------------------------------------------------------------- the same terms on the device (csrc/occ_loss.hip)
+def logit_rows(logits):
+    """[B,C,...] or [P,C] logits -> the [P,C] float32 rows the kernels read IN PLACE: unit column stride, row stride ld >= C.  The
+    NCDHW tensor ``forward_train`` hands to ``OccHead.loss`` is a permuted view of exactly such rows and comes back as a view (no
+    copy); any other layout goes through ``.contiguous()``."""
+    C = logits.shape[1]
+    rows = logits.movedim(1, -1).reshape(-1, C) if logits.dim() > 2 else logits
+    if rows.dtype != torch.float32:
+        rows = rows.float()
+    if (C > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) < C):
+        rows = rows.contiguous()
+    return rows
+
+
+def _device_only(name, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            from ._lib import CooccError
+            raise CooccError("%s runs on the GPU only; got a %s tensor (the eager functions of co_occ_amd.losses take CPU tensors)"
+                             % (name, t.device))
+
+
+def _labels_u8(t):
+    return (t if t.dtype == torch.uint8 else t.to(torch.uint8)).contiguous()
+
+
+def occ_loss_terms_device(logits, target, class_weights=None, empty_idx=0, ignore_index=255, coords=None):
+    """The four unweighted terms (ce_ssc_loss, sem_scal_loss, geo_scal_loss, lovasz_softmax of the softmax) of ``logits`` ([B,C,...] or
+    [P,C]) against ``target`` ([B,...] or [P] labels, ``ignore_index`` = ignore) as ONE differentiable [4] tensor: HIP kernels forward
+    and backward, no host read, bitwise reproducible.  ``coords`` ([3,P] int64): ``target`` is the label volume [B,X,Y,Z] and row i is
+    judged against ``target[0, coords[0,i], coords[1,i], coords[2,i]]`` (OccHead.loss_point's gather, done in the kernel)."""
+    _device_only("occ_loss_terms_device", logits, target, class_weights, coords)
+    if ignore_index != 255:
+        raise ValueError("occ_loss_terms_device: ignore_index is 255 (uint8 labels), got %r" % (ignore_index,))
+    from .autograd import OccLossFn
+    rows = logit_rows(logits)
+    if class_weights is not None:
+        class_weights = class_weights.float().contiguous()
+        if class_weights.numel() != rows.shape[1]:
+            raise ValueError("occ_loss_terms_device: %d class weights for %d classes" % (class_weights.numel(), rows.shape[1]))
+    if coords is not None:
+        labels, coords = _labels_u8(target[0]), coords.long().contiguous()
+        if coords.shape != (3, rows.shape[0]):
+            raise ValueError("occ_loss_terms_device: coords %s for %d rows" % (tuple(coords.shape), rows.shape[0]))
+    else:
+        labels = _labels_u8(target.reshape(-1))
+        if labels.numel() != rows.shape[0]:
+            raise ValueError("occ_loss_terms_device: %d labels for %d rows" % (labels.numel(), rows.shape[0]))
+    return OccLossFn.apply(rows, labels, coords, class_weights, empty_idx)
+
+
+def pool_labels_device(target_voxels, H, W, D, empty_idx=0, num_cls=17, dtype=torch.long):
+    """``pool_labels`` as one HIP kernel (a thread per coarse cell): the same integers.  Ratios 1, 2 and 4."""
+    _device_only("pool_labels_device", target_voxels)
+    from ._lib import call, ptr
+    B = target_voxels.shape[0]
+    ratio = target_voxels.shape[1] // H
+    vol = _labels_u8(target_voxels)
+    if tuple(vol.shape) != (B, H * ratio, W * ratio, D * ratio):
+        raise ValueError("pool_labels_device: volume %s is not %d x the grid (%d, %d, %d)" % (tuple(vol.shape), ratio, H, W, D))
+    out = torch.empty(B, H, W, D, device=vol.device, dtype=torch.uint8)
+    call("coocc_pool_labels", ptr(vol), B, H, W, D, ratio, int(empty_idx), int(num_cls), ptr(out))
+    return out if dtype == torch.uint8 else out.to(dtype)

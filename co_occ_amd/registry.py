@@ -73,7 +73,8 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
     return DETECTORS.build(dict(cfg, **overrides))
 
 
-def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False):
+def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False,
+                        device_occ_losses=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -85,8 +86,11 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     ``COOCC_Ray_L`` with its ``train_lidar_trunk`` option on by default, so an unchanged coocc_lidar.py config trains SECOND3D /
     SECOND3DFPN on the HIP engine.  ``train_sparse_encoder_hd=True`` (with ``sparse_encoder_hd=True``) registers a
     ``SparseEncoderHD`` whose ``train_enabled`` is on, so the reference's own detector trains it under ``train()``; with
-    ``detectors=True`` our ``COOCC_Ray_L`` is registered with the option on by default as well.  Returns False when mmdet / mmdet3d
-    are not importable."""
+    ``detectors=True`` our ``COOCC_Ray_L`` is registered with the option on by default as well.  ``device_occ_losses=True`` (with
+    ``detectors=True``) registers ``COOCC_Ray`` and ``COOCC_Ray_L`` with their ``device_occ_losses`` option on by default: OccHead's
+    loss terms and their gradient are computed on the device.  Returns False when mmdet / mmdet3d are not importable."""
+    if device_occ_losses and not detectors:
+        raise ValueError("register_into_mmdet: device_occ_losses=True is an option of this package's detectors; pass detectors=True")
     if train_lidar_trunk and not detectors:
         raise ValueError("register_into_mmdet: train_lidar_trunk=True is an option of this package's COOCC_Ray_L; pass detectors=True")
     if train_sparse_encoder_hd and not sparse_encoder_hd:
@@ -113,7 +117,23 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     if detectors and (train_lidar_trunk or train_sparse_encoder_hd):
         mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True,
                                      module=trunk_training_detector(train_lidar_trunk, train_sparse_encoder_hd))
+    if detectors and device_occ_losses:
+        for name in ("COOCC_Ray", "COOCC_Ray_L"):
+            mb.DETECTORS.register_module(name=name, force=True, module=device_occ_losses_detector(mb.DETECTORS.module_dict[name]))
     return True
+
+
+def device_occ_losses_detector(base):
+    """``base`` (``COOCC_Ray`` / ``COOCC_Ray_L``, possibly already a ``trunk_training_detector``) whose ``device_occ_losses`` option is
+    on by default (what ``register_into_mmdet(detectors=True, device_occ_losses=True)`` puts into mmdet's registry)."""
+    if isinstance(base, str):
+        base = DETECTORS.get(base)
+
+    class _Det(base):
+        def __init__(self, *args, device_occ_losses=True, **kwargs):
+            super().__init__(*args, device_occ_losses=device_occ_losses, **kwargs)
+    _Det.__name__ = _Det.__qualname__ = base.__name__
+    return _Det
 
 
 def trunk_training_detector(train_lidar_trunk=True, train_sparse_encoder_hd=False):

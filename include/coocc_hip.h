@@ -888,6 +888,28 @@ int coocc_sparse_dgrad_table3(const int32_t* in_coors, int Mi, int Di, int Hi, i
 int coocc_bn_apply_ex(const float* x, int M, int C, const float* mean, const float* var, const float* gamma, const float* beta,
                       float eps, const float* res, int relu, float* y, void* out_h2, void* stream);
 
+/* ---- the OccHead losses on the device (co_occ_amd/losses.py occ_loss_terms_device, csrc/occ_loss.hip) */
+#define COOCC_OCC_LOSS_STATS 208 /* doubles of the statistics block coocc_occ_loss_fwd saves for coocc_occ_loss_bwd */
+/* Majority-vote label pooling of OccHead.loss_voxel (occ_head.py:269-281; the integers of losses.pool_labels): uint8 label volume
+ * [B][H*ratio][W*ratio][D*ratio] (255 = ignore) -> uint8 [B][H][W][D].  ratio 1 (a copy), 2 or 4; any other is refused. */
+int coocc_pool_labels(const uint8_t* vol, int B, int H, int W, int D, int ratio, int empty_idx, int num_cls, uint8_t* out,
+                      void* stream);
+/* Bytes of workspace coocc_occ_loss_fwd needs for P rows of C classes (sort buffers, partial sums, rocPRIM's temporary storage). */
+size_t coocc_occ_loss_ws(int64_t P, int C);
+/* The four unweighted terms out[4] = (ce, sem_scal, geo_scal, lovasz) of logits [P][ld] (C <= ld, C <= 32 classes, read in place)
+ * against uint8 labels (255 = ignore; other values outside [0, C) are ignored as well).  labels: [P], or with coords ([3][P] int64)
+ * the label volume [VX][VY][VZ] that is read at the coordinates (loss_point's gather; a coordinate outside the volume is ignored).
+ * row_labels ([P], optional without coords): the label each row was given.  class_w: optional [C] weights of the cross-entropy.
+ * Writes stats[COOCC_OCC_LOSS_STATS] and lov_w [P][C] (the Lovasz weight of every valid row and present class; the rest is left
+ * unwritten and never read) for the backward.  fp32 softmax, every reduction in fp64 in a fixed order; no host read, no allocation. */
+int coocc_occ_loss_fwd(const float* logits, int64_t P, int C, int ld, const uint8_t* labels, const int64_t* coords, int VX, int VY,
+                       int VZ, uint8_t* row_labels, const float* class_w, int empty_idx, float* out, double* stats, float* lov_w,
+                       void* ws, size_t ws_bytes, void* stream);
+/* d(sum_k gout[k] * out[k]) / dlogits -> dlogits [P][ldg] (columns 0..C-1), one pass over the rows; rows labelled 255 get exactly 0.
+ * row_labels: [P] (the forward's labels, or its row_labels output); gout: [4] on the DEVICE. */
+int coocc_occ_loss_bwd(const float* logits, int64_t P, int C, int ld, const uint8_t* row_labels, const float* class_w, int empty_idx,
+                       const double* stats, const float* lov_w, const float* gout, float* dlogits, int ldg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
