@@ -26,8 +26,9 @@ TRAIN_H2 = __import__("os").environ.get("COOCC_TRAIN_H2", "1") != "0"
 # BatchNorm, and an f16 is subnormal below 6.1e-5 (with a mean-reduced loss over 640 k voxels |dy| ~ 1e-6: the hi half alone would
 # keep a handful of bits).  So the gradient operand gets a per-tensor power-of-two scale chosen ON THE DEVICE: the epilogue-backward
 # pass that produces dacc also collects max |dacc| (coocc_conv_epilogue_bwd_ex), a one-thread kernel turns it into {2^k, 2^-k} with
-# max |dacc| 2^k in [TARGET / 2, TARGET), the operand writers multiply by the first word and the GEMM's alpha by the second --
-# exact, no host read, any loss scale.  TARGET = 1024 leaves the F(4x4) input transform (x 100 / 8) inside the f16 range.
+# max |dacc| 2^k in [TARGET, 2 TARGET) (TARGET a power of two: k is the difference of the two frexp exponents), the operand writers
+# multiply by the first word and the GEMM's alpha by the second -- exact, no host read, any loss scale.  TARGET = 1024 leaves the
+# F(4x4) input transform (x 100 / 8) inside the f16 range: 2048 x 12.5 = 25600 < 65504.
 # COOCC_TRAIN_H2_DGRAD=0: dgrad on the fp32-MFMA kernels.
 TRAIN_H2_DGRAD = TRAIN_H2 and __import__("os").environ.get("COOCC_TRAIN_H2_DGRAD", "1") != "0"
 TRAIN_H2_GRAD_TARGET = 1024.0
@@ -198,8 +199,8 @@ def _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw, gscale=None):
         return False
     if TRAIN_H2_WGRAD and gscale is not None and core.CONV_ENGINE == "h2" and Z in (2, 4, 8) and Cin % 4 == 0 and Cout % 4 == 0:
         # both operands straight into the voxel-major split-f16 form (no fp32 V / dM): V (|V| <= 100 |x|) with the forward path's
-        # static scale; dM = A dY A^T amplifies by up to 15^2 on top of the device-chosen gradient scale (max |dacc| -> [512, 1024)):
-        # 1/16 keeps it below the f16 range
+        # static scale; dM = A dY A^T amplifies by up to 15^2 on top of the device-chosen gradient scale (max |dacc| -> [1024, 2048)):
+        # 1/16 keeps it below the f16 range and the range guard (2048 x 225 / 16 = 28800 < 32768)
         vs, ms = core.H2_WINO_SCALE[tile], 1.0 / 16.0
         Vk = core._wino_buffer(dev, "Vk", pts * G * Cin)
         Mk = core._wino_buffer(dev, "Mk", pts * G * Cout)

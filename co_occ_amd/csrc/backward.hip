@@ -523,6 +523,36 @@ extern "C" int coocc_fine_sample_voxel_bwd(const float* dfeat, int dfeat_stride,
 //   dxhat = dy * [y > 0] * gamma;   dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat))
 //   dgamma = sum_rows dy' * xhat,   dbeta = sum_rows dy'     (column sums: per-block partials in LDS, then fp32 atomics)
 // x is the PRE-norm input (the forward kernel works in place, so the caller keeps a copy), y the post-ReLU output.
+// Statistics as the forward takes them (gn_group_stats: Acc = double for wide groups, whose two group means are summed in it as
+// well).  dxhat is ONE rounded product in both loops (mul_unfused: never fused into the subtraction of its mean), so a group of one
+// channel gives dx = 0 exactly.
+template <typename Acc>
+__device__ __forceinline__ void groupnorm_rows_bwd_group(const float* __restrict__ px, const float* __restrict__ py,
+                                                         const float* __restrict__ pdy, int cpg, const float* __restrict__ gamma,
+                                                         float eps, int relu, float* __restrict__ pdx, float* s_dgamma,
+                                                         float* s_dbeta) {
+  Acc mean;
+  float rstd;
+  gn_group_stats<Acc>(px, cpg, eps, mean, rstd);
+  Acc m1 = 0, m2 = 0;
+  for (int c = 0; c < cpg; ++c) {
+    const float xh = (float)(px[c] - mean) * rstd;
+    float g_ = pdy[c];
+    if (relu && !(py[c] > 0.f)) g_ = 0.f;
+    atomicAdd(&s_dgamma[c], g_ * xh);
+    atomicAdd(&s_dbeta[c], g_);
+    const float dxh = mul_unfused(g_, gamma[c]);
+    m1 += dxh; m2 += (Acc)dxh * xh;
+  }
+  m1 /= (Acc)cpg; m2 /= (Acc)cpg;
+  for (int c = 0; c < cpg; ++c) {
+    const float xh = (float)(px[c] - mean) * rstd;
+    float g_ = pdy[c];
+    if (relu && !(py[c] > 0.f)) g_ = 0.f;
+    pdx[c] = rstd * (mul_unfused(g_, gamma[c]) - (float)m1 - xh * (float)m2);
+  }
+}
+
 __global__ __launch_bounds__(256) void k_groupnorm_rows_bwd(const float* __restrict__ x, const float* __restrict__ y,
                                                              const float* __restrict__ dy, long long n, int C, int stride,
                                                              int groups, const float* __restrict__ gamma, float eps, int relu,
@@ -539,30 +569,11 @@ __global__ __launch_bounds__(256) void k_groupnorm_rows_bwd(const float* __restr
     const float* px = x + row * stride + g * cpg;
     const float* pdy = dy + row * stride + g * cpg;
     const float* py = y + row * stride + g * cpg;
-    float mean = 0.f;
-    for (int c = 0; c < cpg; ++c) mean += px[c];
-    mean /= (float)cpg;
-    float var = 0.f;
-    for (int c = 0; c < cpg; ++c) { float d = px[c] - mean; var += d * d; }
-    var /= (float)cpg;
-    const float rstd = 1.f / sqrtf(var + eps);
-    float m1 = 0.f, m2 = 0.f;
-    for (int c = 0; c < cpg; ++c) {
-      const float xh = (px[c] - mean) * rstd;
-      float g_ = pdy[c];
-      if (relu && !(py[c] > 0.f)) g_ = 0.f;
-      atomicAdd(&s_part[g * cpg + c], g_ * xh);
-      atomicAdd(&s_part[C + g * cpg + c], g_);
-      const float dxh = g_ * gamma[g * cpg + c];
-      m1 += dxh; m2 += dxh * xh;
-    }
-    m1 /= (float)cpg; m2 /= (float)cpg;
-    for (int c = 0; c < cpg; ++c) {
-      const float xh = (px[c] - mean) * rstd;
-      float g_ = pdy[c];
-      if (relu && !(py[c] > 0.f)) g_ = 0.f;
-      dx[row * stride + g * cpg + c] = rstd * (g_ * gamma[g * cpg + c] - m1 - xh * m2);
-    }
+    float* pdx = dx + row * stride + g * cpg;
+    if (cpg > GN_WIDE_GROUP)
+      groupnorm_rows_bwd_group<double>(px, py, pdy, cpg, gamma + g * cpg, eps, relu, pdx, s_part + g * cpg, s_part + C + g * cpg);
+    else
+      groupnorm_rows_bwd_group<float>(px, py, pdy, cpg, gamma + g * cpg, eps, relu, pdx, s_part + g * cpg, s_part + C + g * cpg);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {

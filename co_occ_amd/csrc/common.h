@@ -42,6 +42,29 @@ int coocc_set_error(int code, const char* fmt, ...);
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
+// Mean and rstd (two-pass, biased variance) of the cpg channels one thread of the row-wise GroupNorm kernels walks (k_groupnorm_rows,
+// k_groupnorm_rows_bwd).  Acc = float: the sequential fp32 sums of the 4-channel groups of the fine branch.  Groups wider than
+// GN_WIDE_GROUP take Acc = double, and keep the mean in it for x - mean: a sequential fp32 sum over thousands of channels put y at
+// 5-11 x the fp32 noise floor from float64, and the fp32 rounding of the mean is an ABSOLUTE error of xhat that dgamma's terms near
+// xhat = 0 do not forgive (tests/test_gpu_norm.py, C / groups = 2048).
+constexpr int GN_WIDE_GROUP = 64;
+template <typename Acc>
+__device__ __forceinline__ void gn_group_stats(const float* __restrict__ p, int cpg, float eps, Acc& mean, float& rstd) {
+  mean = 0;
+  for (int c = 0; c < cpg; ++c) mean += p[c];
+  mean /= (Acc)cpg;
+  Acc var = 0;
+  for (int c = 0; c < cpg; ++c) { Acc d = p[c] - mean; var += d * d; }
+  var /= (Acc)cpg;
+  rstd = 1.f / sqrtf((float)var + eps);
+}
+
+// a * b rounded to fp32 and never fused into an addition that consumes it
+__device__ __forceinline__ float mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // squared distance with the contraction nvcc applies to the reference expression
 // (furthest_point_sample_cuda.cu:65-66, ball_query_cuda.cu:41-42); see oracle/c/coocc_oracle.c.
 __device__ __forceinline__ float sqdist3(float x1, float y1, float z1, float x2, float y2,

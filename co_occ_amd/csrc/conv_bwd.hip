@@ -271,7 +271,8 @@ __global__ __launch_bounds__(256) void k_colsum_final4(const double* __restrict_
   if ((threadIdx.x >> 2) == 0 && c < C) dbias[c] = accumulate ? dbias[c] + (float)t[0] : (float)t[0];
 }
 
-// scale2 = {2^k, 2^-k} with amax * 2^k in [target / 2, target) (k = 0 for an all-zero gradient); the slots are left zero for the next pass
+// scale2 = {2^k, 2^-k}, k = e_target - e_amax of frexp (|k| <= 100): amax * 2^k in [2^(e_target - 1), 2^e_target), that is [target, 2 target)
+// for a power-of-two target (k = 0 for an all-zero or non-finite gradient); the slots are left zero for the next pass
 __global__ __launch_bounds__(64) void k_amax_scale(uint32_t* __restrict__ amax_word, float target, float* __restrict__ scale2) {
   uint32_t v = amax_word[threadIdx.x * AMAX_STRIDE];
   amax_word[threadIdx.x * AMAX_STRIDE] = 0u;

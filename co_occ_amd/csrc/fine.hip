@@ -592,6 +592,18 @@ static int fine_sample_img_impl(const float* img_nhwc, int ncam, int Ci, int Hf,
 }
 
 // nn.GroupNorm over rows [n, C] (2-D input: statistics per row and group) + optional ReLU
+template <typename Acc>
+__device__ __forceinline__ void groupnorm_rows_group(float* p, int cpg, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     float eps, int relu) {
+  Acc mean;
+  float rstd;
+  gn_group_stats<Acc>(p, cpg, eps, mean, rstd);
+  for (int c = 0; c < cpg; ++c) {
+    float v = (float)(p[c] - mean) * rstd * gamma[c] + beta[c];
+    p[c] = relu ? fmaxf(v, 0.f) : v;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_groupnorm_rows(float* __restrict__ x, long long n, int C, int stride, int groups,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          float eps, int relu) {
@@ -601,17 +613,8 @@ __global__ __launch_bounds__(256) void k_groupnorm_rows(float* __restrict__ x, l
   int g = (int)(i - row * groups);
   int cpg = C / groups;
   float* p = x + row * stride + g * cpg;
-  float mean = 0.f;
-  for (int c = 0; c < cpg; ++c) mean += p[c];
-  mean /= (float)cpg;
-  float var = 0.f;
-  for (int c = 0; c < cpg; ++c) { float d = p[c] - mean; var += d * d; }
-  var /= (float)cpg;
-  float rstd = 1.f / sqrtf(var + eps);
-  for (int c = 0; c < cpg; ++c) {
-    float v = (p[c] - mean) * rstd * gamma[g * cpg + c] + beta[g * cpg + c];
-    p[c] = relu ? fmaxf(v, 0.f) : v;
-  }
+  if (cpg > GN_WIDE_GROUP) groupnorm_rows_group<double>(p, cpg, gamma + g * cpg, beta + g * cpg, eps, relu);
+  else groupnorm_rows_group<float>(p, cpg, gamma + g * cpg, beta + g * cpg, eps, relu);
 }
 
 extern "C" int coocc_groupnorm_rows(float* x, int64_t n, int C, int stride, int groups, const float* gamma,

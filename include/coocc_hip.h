@@ -408,10 +408,12 @@ int coocc_conv_epilogue_bwd(const float* dout, int dout_stride, const float* out
                             float* dres, int dres_stride, int dres_accumulate, float* dbias,
                             int dbias_accumulate, float* ws, int64_t ws_floats, void* stream);
 /* ... and the operand scale of the split-f16 engine for dacc, chosen on the device: amax_word (COOCC_AMAX_WORDS zeroed 32-bit
- * words, left zero: the workgroups spread their atomics over 64 of them, 128 bytes apart) collects max |dacc| during the pass, then scale2[0] = the power of two that brings it into [target / 2, target) (1 when the
- * gradient is all zero), scale2[1] = its inverse.  The gradient operand of a dgrad / wgrad GEMM is written as H2 rows with
+ * words, left zero: the workgroups spread their atomics over 64 of them, 128 bytes apart) collects max |dacc| during the pass, then
+ * scale2[0] = 2^k with k = e_target - e_amax of frexp (x = m 2^e, m in [0.5, 1); |k| <= 100), which brings max |dacc| into
+ * [2^(e_target - 1), 2^e_target) -- [target, 2 target) for a target that is a power of two, [1024, 2048) for 1024 -- (1 when the
+ * gradient is all zero or not finite), scale2[1] = its inverse.  The gradient operand of a dgrad / wgrad GEMM is written as H2 rows with
  * scale_dev = scale2 (coocc_rows_to_h2_ex, coocc_wino_input_h2_ex) and the GEMM undoes it with coocc_conv_desc.alpha_dev =
- * scale2 + 1: whatever the loss scale, the f16 halves see values of magnitude <= target (an f16 is subnormal below 6.1e-5; the
+ * scale2 + 1: whatever the loss scale, the f16 halves see values of magnitude < 2^e_target (an f16 is subnormal below 6.1e-5; the
  * reference's cuDNN backward has no such concern, resnet3d.py:34-64).  amax_word / scale2 NULL: coocc_conv_epilogue_bwd. */
 #define COOCC_AMAX_WORDS 2048
 int coocc_conv_epilogue_bwd_ex(const float* dout, int dout_stride, const float* out, int out_stride,

@@ -163,7 +163,12 @@ def test_forward_train_with_the_reference_call_signature(dev):
     """tools/train.py path: ``model(return_loss=True, points=, img_metas=, img_inputs=, gt_occ=)`` -> the reference's loss
     dict (coocc_ray.py:339-434); training-mode BN (batch statistics, running stats updated); gradients reach every
     hot-path parameter -- the sparse LiDAR encoder included (round 5: it trains like upstream, batch-statistics BN1d) -- and
-    flow back into the upstream encoders; ``freeze_lidar_encoder()`` keeps the LiDAR branch fixed."""
+    flow back into the upstream encoders; ``freeze_lidar_encoder()`` keeps the LiDAR branch fixed.
+
+    ``conv_input`` is SparseConv -> GroupNorm(16, base_channel = 16): groups of ONE channel, whose output is beta whatever the
+    convolution gives, so the gradient of that convolution's weight is exactly zero (the GroupNorm's own beta and the next
+    convolution are where the LiDAR gradient shows).  An earlier form of this test asked for a non-zero weight gradient there and
+    got one from a rounding residual of k_groupnorm_rows_bwd (tests/test_gpu_norm.py, the one-channel-per-group case)."""
     model = _full_model(dev)
     model.freeze_lidar_encoder()
     model.train()
@@ -185,7 +190,11 @@ def test_forward_train_with_the_reference_call_signature(dev):
     missing = [n for n, p in model.named_parameters() if p.requires_grad and p.grad is None
                and "frustum" not in n and n.split(".")[-1] not in ("dx", "bx", "nx")]
     assert not missing, missing[:8]
-    assert float(model.pts_middle_encoder.conv_input[0].weight.grad.abs().sum()) > 0     # ... and the first sparse convolution
+    enc = model.pts_middle_encoder
+    assert enc.conv_input[1].num_groups == enc.conv_input[1].num_channels          # one channel per group:
+    assert float(enc.conv_input[0].weight.grad.abs().sum()) == 0.0                 # ... nothing passes the GroupNorm, exactly
+    assert float(enc.conv_input[1].bias.grad.abs().sum()) > 0                      # ... its beta is what the first layer learns
+    assert float(enc.conv1[0][0].weight.grad.abs().sum()) > 0                      # ... and the first sparse convolution behind it
     assert not torch.equal(lrm0, model.pts_middle_encoder.conv1[0][1].running_mean)
     assert all(torch.isfinite(p.grad).all() for p in model.parameters() if p.grad is not None)
     assert float(model.img_backbone.conv.weight.grad.abs().sum()) > 0          # lift (x) splat backward reaches the image branch
