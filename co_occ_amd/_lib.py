@@ -183,6 +183,7 @@ SIGNATURES = {
     "coocc_lidarseg_points": (I, [P, L, L, L, L, I, I, I, I, P, L, L, I, I, P, I, I, P, P, I, P, P]),
     "coocc_render_eval_stats": (L, [P, P, P, P, I, I, I, P, P, Z, P]),
     "coocc_render_panels": (I, [P, P, P, P, I, I, I, P, P]),
+    "coocc_render_eval_ssim": (L, [P, P, I, I, I, ctypes.c_double, P, P, Z, P]),
     "coocc_sparse_dgrad_table3": (I, [P] + [I] * 16 + [P, P, P, P]),
     "coocc_bn_apply_ex": (I, [P, I, I, P, P, P, P, F, P, I, P, P, P]),
     "coocc_pool_labels": (I, [P, I, I, I, I, I, I, I, P, P]),

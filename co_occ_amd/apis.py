@@ -122,7 +122,8 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
     = what ``COOCC_Ray.simple_test`` returns for that sample (same tensors, same metrics, fine outputs trimmed to their exact
     size).  ``data``: the keyword arguments of ``simple_test`` (``img_inputs`` / ``img``, ``points``, ``gt_occ``,
     ``visible_mask``, ``points_occ``, ``img_metas``, ``gt_depths``, ``precomputed``).  With ``model.render_eval`` the render keys
-    (``psnr``, ``psnr_mean``, ``depth_sq_err``, ``depth_valid``) are computed the same way (``coocc_render_eval_stats``).
+    (``psnr``, ``psnr_mean``, ``depth_sq_err``, ``depth_valid``) are computed the same way (``coocc_render_eval_stats``), and with
+    ``model.render_ssim`` on top of it ``ssim`` / ``ssim_mean`` (``coocc_render_eval_ssim``).
 
     Nothing in the loop waits for the sample that was just issued: the encoders upstream of the hot path run eagerly at submit
     time; pooling + index search of the next ``ahead`` samples are prefetched under the dense stages (one captured hipGraph
@@ -167,7 +168,7 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
                     parts.append(lseg[1].reshape(-1))
             if out.get("fine_count") is not None:
                 parts.append(out["fine_count"].reshape(-1).to(torch.int64))
-            reval = None
+            reval = rssim = None
             if model.render_eval:
                 # the render stats read the slot's maps: here, before the slot can be reused; the float64 block rides in the
                 # same pinned-host copy, bit for bit (viewed as int64)
@@ -177,6 +178,10 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
                     if torch.is_tensor(g) and g.is_cuda:
                         g.record_stream(ds)
                 reval = model._render_eval_launch(out, gi, gdep)
+                # the SSIM block likewise, right behind the stats launch; in the host buffer it sits IN FRONT of the render stats
+                rssim = model._render_ssim_launch(out, gi)
+                if rssim is not None and not model.metrics_on_device:
+                    parts.append(rssim.view(torch.int64).reshape(-1))
                 if reval is not None and not model.metrics_on_device:
                     parts.append(reval[0].view(torch.int64).reshape(-1))
             host = ev = None
@@ -187,20 +192,20 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
             from . import streams as cstreams
             ev = cstreams.new_event()           # fires after the pinned-host copy above: a copy command, complete when it does
             ev.record(ds)
-        return (data, t, (out, host, both if gt is not None else None, lseg, reval), ev)
+        return (data, t, (out, host, both if gt is not None else None, lseg, reval, rssim), ev)
 
     def finish(item):
         data, t, payload, ev = item
         if t is None:
             return data, payload
-        out, host, both, lseg, reval = payload
+        out, host, both, lseg, reval, rssim = payload
         ev.synchronize()
         from . import core
         core.check_h2_overflow()
         out = dict(out)
         gt, vm = data.get("gt_occ"), data.get("visible_mask")
         C = ncls_of(out)
-        nm = nl = 0                               # host buffer: [ metrics (nm) | lidarseg matrix (nl) | fine count | render stats ]
+        nm = nl = 0                               # host buffer: [ metrics (nm) | lidarseg matrix (nl) | fine count | ssim block | render stats ]
         if gt is not None:
             nm = both.numel()
         if lseg is not None and not model.metrics_on_device:
@@ -219,11 +224,19 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
         if lseg is not None:
             hist = lseg[1] if model.metrics_on_device else host[nm:nm + nl].numpy().copy()
             out.update(model._lidarseg_finish(lseg[0], hist, data["points_occ"]))
+        nr = 0                                    # int64 words of the render stats at the end of the host buffer
         if reval is not None:
             block = reval[0]
             if not model.metrics_on_device:
-                block = host[host.numel() - block.numel():].view(torch.float64).numpy().reshape(block.shape).copy()
+                nr = block.numel()
+                block = host[host.numel() - nr:].view(torch.float64).numpy().reshape(block.shape).copy()
             out.update(model._render_eval_finish(block, *reval[1:]))
+        if rssim is not None:
+            block = rssim
+            if not model.metrics_on_device:
+                end = host.numel() - nr
+                block = host[end - block.numel():end].view(torch.float64).numpy().reshape(block.shape).copy()
+            out.update(model._render_ssim_finish(block))
         return data, out
 
     try:

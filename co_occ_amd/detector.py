@@ -104,7 +104,7 @@ class COOCC_Ray(nn.Module):
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
-                 train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, **kwargs):
+                 train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, render_ssim=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -154,6 +154,9 @@ class COOCC_Ray(nn.Module):
         # depth error of save_rendered_img.py:39-79 when gt_depths carries a map) on the device.  Upstream runs that branch
         # unconditionally, prints, and writes ./img_<v>.png; here nothing is printed or written (apis.save_rendered_panels does)
         self.render_eval = bool(render_eval)
+        # opt-in, on top of ``render_eval``: the SSIM of the rendered colour maps too (the second member of save_rendered_img's
+        # triple, save_rendered_img.py:22-37), on the device.  Detectors that render no colour (COOCC_Ray_L) never report it
+        self.render_ssim = bool(render_ssim)
         # eval-mode ``simple_test`` runs its dense stage as ONE captured hipGraph launch (co_occ_amd.serving, one slot, results
         # identical to the eager path); COOCC_SIMPLE_TEST_GRAPH=0 or ``model.graph_simple_test = False`` keeps every launch eager
         self.graph_simple_test = __import__("os").environ.get("COOCC_SIMPLE_TEST_GRAPH", "1") != "0"
@@ -542,19 +545,23 @@ class COOCC_Ray(nn.Module):
         """The tail of ``simple_test`` (coocc_ray.py:539-560, 629-656) on a decoded sample: the reference's result keys and,
         with ground truth, the SC / SSC confusion matrices; with ``points_occ``, the lidarseg keys; with ``render_eval`` set, rendered
         maps and ``gt_img``, the render keys ``psnr`` [N] / ``psnr_mean`` (+ ``depth_sq_err`` / ``depth_valid`` [N] when ``gt_depths``
-        gives a map of the maps' size) -- numpy like the other metrics, device tensors under ``metrics_on_device``."""
+        gives a map of the maps' size; + ``ssim`` [N] / ``ssim_mean`` with ``render_ssim`` and colour maps) -- numpy like the other
+        metrics, device tensors under ``metrics_on_device``."""
         out = dict(out)
         out.update(output_voxels=out["pred_c"], target_voxels=gt_occ)
         lseg = self._lidarseg_launch(out, points_occ, img_metas) if points_occ else None
         reval = self._render_eval_launch(out, gt_img, gt_depths)
+        rssim = self._render_ssim_launch(out, gt_img)
         if reval is not None:
             out.update(self._render_eval_finish(reval[0] if self.metrics_on_device else reval[0].cpu().numpy(), *reval[1:]))
+        if rssim is not None:
+            out.update(self._render_ssim_finish(rssim if self.metrics_on_device else rssim.cpu().numpy()))
         if gt_occ is not None:
             out.update(self._metrics(out, gt_occ, visible_mask))
         if lseg is not None:
             labels, hist = lseg
             out.update(self._lidarseg_finish(labels, hist if self.metrics_on_device else hist.cpu().numpy(), points_occ))
-        if (gt_occ is not None or lseg is not None or reval is not None) and not self.metrics_on_device:
+        if (gt_occ is not None or lseg is not None or reval is not None or rssim is not None) and not self.metrics_on_device:
             from . import core
             core.check_h2_overflow()          # the metrics were read back: the whole sample has finished on this stream
         return out
@@ -594,6 +601,22 @@ class COOCC_Ray(nn.Module):
         """The render keys of a stats block: the host copy (numpy) or the device tensor (``metrics_on_device``)."""
         from .evaluation import render_eval_keys
         return render_eval_keys(block, with_rgb, with_depth, extrema=False)
+
+    def _render_ssim_launch(self, out, gt_img):
+        """The SSIM block of the sample's rendered colour maps (``coocc_render_eval_ssim``) on the CURRENT stream, right behind
+        the stats launch -> float64 [N,8], or None unless ``render_eval`` and ``render_ssim`` are both set, colour maps were
+        rendered and ``gt_img`` is there.  No synchronisation."""
+        if not (self.render_eval and self.render_ssim) or out.get("rgbs") is None or gt_img is None:
+            return None
+        from .evaluation import render_ssim
+        return render_ssim(out["rgbs"], gt_img)
+
+    @staticmethod
+    def _render_ssim_finish(block):
+        """``ssim`` / ``ssim_mean`` of an SSIM block: the host copy (numpy) or the device tensor (``metrics_on_device``)."""
+        from .evaluation import render_ssim_keys
+        keys = render_ssim_keys(block)
+        return dict(ssim=keys["ssim"], ssim_mean=keys["ssim_mean"])
 
     def _lidarseg_launch(self, out, points_occ, img_metas=None):
         """coocc_ray.py:556-560 on the device: the eval labels of ``forward_lidarseg`` (argmax of the softmax over classes

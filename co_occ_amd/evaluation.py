@@ -11,7 +11,8 @@ coocc_ray.py:693-700) take the same route: ``lidarseg_points`` samples the logit
 16x16 ``fast_hist_crop`` matrix in one kernel; ``LidarSegEvaluator`` accumulates it over a dataset.
 
 The rendered maps of ``test_rendering`` (coocc_ray.py:626-637, P/utils/save_rendered_img.py) are judged the same way:
-``render_eval`` gives the per-view PSNR, the depth error and the comparison panels from two kernels; ``RenderEvaluator``
+``render_eval`` gives the per-view PSNR, the depth error and the comparison panels from two kernels and, on request, the SSIM of
+the colour maps (``render_ssim``, skimage's ``structural_similarity`` as save_rendered_img.py:22-37 calls it); ``RenderEvaluator``
 accumulates them over a dataset."""
 import contextlib
 import warnings
@@ -271,11 +272,74 @@ def render_eval_keys(block, with_rgb=True, with_depth=False, extrema=True):
     return res
 
 
-def render_eval(rgbs, depths, gt_img, gt_depth=None, panels=False, stream=None):
+# SSIM of the colour maps, the second member of the triple save_rendered_img returns (save_rendered_img.py:22-37, 39-79).  Columns
+# of the [N, 8] float64 block (include/coocc_hip.h, coocc_render_eval_ssim): the three channel means, the view's value, the mean
+# over the views, the window count (H-6)(W-6), data_range:
+RS_C0, RS_C1, RS_C2, RS_SSIM, RS_SSIM_MEAN, RS_COUNT, RS_RANGE = range(7)
+RENDER_SSIM_SLOTS = 8
+SSIM_WINDOW = 7
+
+
+def _check_colour_maps(rgbs, gt_img):
+    for name, t in (("rgbs", rgbs), ("gt_img", gt_img)):
+        if not torch.is_tensor(t):
+            raise TypeError("render_ssim: %s is a %s, not a tensor" % (name, type(t).__name__))
+    if rgbs.dim() != 4 or rgbs.shape[3] != 3:
+        raise ValueError("render_ssim: rgbs %s is not [N, H, W, 3]" % (tuple(rgbs.shape),))
+    N, H, W = rgbs.shape[:3]
+    if tuple(gt_img.shape) != (N, 3, H, W):
+        raise ValueError("render_ssim: gt_img %s does not match the rendered maps %s: the maps are 16 fH x 16 fW and must equal "
+                         "the image size ([N, 3, H, W] = %s expected)" % (tuple(gt_img.shape), tuple(rgbs.shape), (N, 3, H, W)))
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError("render_ssim: maps %s are smaller than the 7 x 7 window" % (tuple(rgbs.shape),))
+    for name, t in (("rgbs", rgbs), ("gt_img", gt_img)):
+        if not t.is_cuda:
+            raise RuntimeError("co_occ_amd.evaluation runs on the HIP device only (%s is a %s tensor; there is no CPU fallback)"
+                               % (name, t.device))
+    return N, H, W
+
+
+def render_ssim(rgbs, gt_img, data_range=2.0, out=None):
+    """``coocc_render_eval_ssim`` on the current stream -> the float64 [N, 8] device block (columns RS_*): the SSIM of every
+    rendered colour map rgbs [N,H,W,3] against gt_img [N,3,H,W] as ``skimage.metrics.structural_similarity(pred, target,
+    channel_axis=-1)`` of scikit-image 0.19.3 defines it (7 x 7 uniform window, sample covariance, mean over the windows that lie
+    inside the image, then over the channels).  ``data_range`` defaults to 2.0: upstream passes none, and skimage 0.19.3 then takes
+    the span of the float dtype's nominal range (-1, 1) whatever the images hold, so 2.0 is what upstream's numbers are computed
+    with; pass 1.0 for images in [0, 1] judged by their own range.  No synchronisation, no host read."""
+    N, H, W = _check_colour_maps(rgbs, gt_img)
+    data_range = float(data_range)
+    if not (0.0 < data_range < float("inf")):
+        raise ValueError("render_ssim: data_range %r must be positive and finite" % (data_range,))
+    rgbs, gt_img = _f32c(rgbs), _f32c(gt_img)
+    if out is None:
+        out = torch.empty(N, RENDER_SSIM_SLOTS, dtype=torch.float64, device=rgbs.device)
+    need = int(load().coocc_render_eval_ssim(None, None, N, H, W, data_range, None, None, 0, None))
+    if need < 0:
+        check(need)
+    ws = torch.empty(need // 8, dtype=torch.float64, device=rgbs.device)
+    call("coocc_render_eval_ssim", ptr(rgbs), ptr(gt_img), N, H, W, data_range, ptr(out, torch.float64), ptr(ws), need)
+    return out
+
+
+def render_ssim_keys(block):
+    """The result keys held by an SSIM block -- a device tensor (the keys stay device tensors: nothing synchronises) or its host
+    copy as a numpy array: ``ssim`` [N] fp32, ``ssim_mean`` fp32 scalar (the mean upstream returns), ``ssim_channels`` [N,3] fp64."""
+    if torch.is_tensor(block):
+        f32 = lambda a: a.to(torch.float32)
+    else:
+        block = np.asarray(block, dtype=np.float64).reshape(-1, RENDER_SSIM_SLOTS)
+        f32 = lambda a: a.astype(np.float32)
+    return dict(ssim=f32(block[:, RS_SSIM]), ssim_mean=f32(block[0, RS_SSIM_MEAN]), ssim_channels=block[:, RS_C0:RS_C2 + 1])
+
+
+def render_eval(rgbs, depths, gt_img, gt_depth=None, panels=False, stream=None, ssim=False, data_range=2.0):
     """PSNR / depth error / comparison panels of rendered maps on the device (``stream``: a torch stream, default the current one).
     Returns device tensors: ``psnr`` [N] fp32, ``psnr_mean`` (the scalar upstream prints), ``depth_min`` / ``depth_max`` [N]; with
     ``gt_depth``: ``depth_sq_err`` [N] fp64 = sum (depth - gt_depth)^2 and ``depth_valid`` [N] int64, over gt_depth > 0; with
-    ``panels=True``: ``panels`` uint8 [N,H,3W,3]; always ``stats``, the raw [N, 8] block."""
+    ``panels=True``: ``panels`` uint8 [N,H,3W,3]; with ``ssim=True`` (colour maps required): ``ssim`` [N] fp32, ``ssim_mean`` and
+    ``ssim_stats``, the raw block of ``render_ssim(rgbs, gt_img, data_range)``; always ``stats``, the raw [N, 8] block."""
+    if ssim and rgbs is None:
+        raise ValueError("render_eval: ssim needs rgbs and gt_img (the depth-only variant has no colour maps)")
     _check_maps(rgbs, depths, gt_img, gt_depth)
     if panels and rgbs is None:
         raise ValueError("render_eval: panels need rgbs and gt_img")
@@ -284,6 +348,10 @@ def render_eval(rgbs, depths, gt_img, gt_depth=None, panels=False, stream=None):
         block = render_eval_stats(rgbs, depths, gt_img, gt_depth)
         res = render_eval_keys(block, rgbs is not None, gt_depth is not None)
         res["stats"] = block
+        if ssim:
+            sblock = render_ssim(rgbs, gt_img, data_range)
+            keys = render_ssim_keys(sblock)
+            res.update(ssim=keys["ssim"], ssim_mean=keys["ssim_mean"], ssim_stats=sblock)
         if panels:
             res["panels"] = render_panels(rgbs, depths, gt_img, block)
     return res
@@ -292,10 +360,11 @@ def render_eval(rgbs, depths, gt_img, gt_depth=None, panels=False, stream=None):
 class RenderEvaluator:
     """Whole-dataset accumulation of the render metrics on the device: ``update`` / ``add`` enqueue a few tiny device operations
     and never synchronise; ``summary`` reads back once.  Sums: psnr over the views, the view count, the squared depth error and
-    its pixel count."""
+    its pixel count; once an SSIM block has been added, the per-view SSIM and its view count too."""
 
     def __init__(self, device="cuda"):
         self.acc = torch.zeros(4, dtype=torch.float64, device=device)       # sum psnr | views | sum sq_depth | sum n_valid
+        self.acc_ssim = None                                                # sum ssim | views, from the first SSIM block on
 
     def add(self, block, with_rgb=True):
         """Add a stats block already computed (``render_eval(...)['stats']``; a device tensor or numpy)."""
@@ -304,10 +373,26 @@ class RenderEvaluator:
         psnr = b[:, RE_PSNR].sum() if with_rgb else b.new_zeros(())
         self.acc += torch.stack([psnr, b.new_tensor(n if with_rgb else 0.0), b[:, RE_SQ_DEPTH].sum(), b[:, RE_NVALID].sum()])
 
-    def update(self, rgbs, depths, gt_img, gt_depth=None):
+    def add_ssim(self, block):
+        """Add an SSIM block already computed (``render_ssim(...)`` / ``render_eval(..., ssim=True)['ssim_stats']``; a device
+        tensor or numpy)."""
+        b = torch.as_tensor(np.asarray(block) if not torch.is_tensor(block) else block).reshape(-1, RENDER_SSIM_SLOTS).to(self.acc)
+        if self.acc_ssim is None:
+            self.acc_ssim = torch.zeros(2, dtype=torch.float64, device=self.acc.device)
+        self.acc_ssim += torch.stack([b[:, RS_SSIM].sum(), b.new_tensor(float(b.shape[0]))])
+
+    def update(self, rgbs, depths, gt_img, gt_depth=None, ssim=False, data_range=2.0):
         self.add(render_eval_stats(rgbs, depths, gt_img, gt_depth), with_rgb=rgbs is not None)
+        if ssim:
+            if rgbs is None:
+                raise ValueError("RenderEvaluator.update: ssim needs rgbs and gt_img")
+            self.add_ssim(render_ssim(rgbs, gt_img, data_range))
 
     def summary(self):
         psnr, views, sq, nv = self.acc.cpu().tolist()
-        return dict(psnr_mean=psnr / views if views else float("nan"), views=int(views), depth_sq_err=sq, depth_valid=int(nv),
-                    depth_mse=sq / nv if nv else float("nan"), depth_rmse=(sq / nv) ** 0.5 if nv else float("nan"))
+        res = dict(psnr_mean=psnr / views if views else float("nan"), views=int(views), depth_sq_err=sq, depth_valid=int(nv),
+                   depth_mse=sq / nv if nv else float("nan"), depth_rmse=(sq / nv) ** 0.5 if nv else float("nan"))
+        if self.acc_ssim is not None:
+            total, n = self.acc_ssim.cpu().tolist()
+            res["ssim_mean"] = total / n if n else float("nan")
+        return res

@@ -806,6 +806,18 @@ int64_t coocc_render_eval_stats(const float* rgbs, const float* depths, const fl
  * device: no host read between the two launches. */
 int coocc_render_panels(const float* rgbs, const float* depths, const float* gt_img, const double* block, int N, int H, int W,
                         uint8_t* panels, void* stream);
+/* SSIM of the rendered colour maps, the second member of save_rendered_img's triple (P/utils/save_rendered_img.py:22-37):
+ * skimage.metrics.structural_similarity(pred, target, channel_axis=-1) of scikit-image 0.19.3 with its defaults -- a 7 x 7 uniform
+ * window (NP = 49), sample covariance (NP / (NP - 1)), C1 = (0.01 R)^2, C2 = (0.03 R)^2 with R = data_range (skimage takes 2.0 for
+ * a float image), S averaged over the (H-6)(W-6) pixels whose whole window lies inside the image.  rgbs:[N,H,W,3], gt_img:[N,3,H,W]
+ * as for coocc_render_eval_stats; H, W >= 7.  Box sums, S and all reductions in fp64.  block:[N,8] doubles (device), per view:
+ *   [0..2] the channel means of S   [3] ([0] + [1] + [2]) / 3 rounded once to fp32   [4] the mean of [3] over the views (sequential
+ *   fp32 sum / N as upstream, repeated in every row)   [5] the window count (H-6)(W-6)   [6] data_range   [7] 0.
+ * One fp64 partial per (tile, channel) in ws, added in a fixed order by the last step: no floating-point atomics, run-to-run
+ * bit-equal, no host read (capturable).  ws == NULL: returns the workspace bytes for (N, H, W) and launches nothing; otherwise 0
+ * or a negative COOCC_E* code. */
+int64_t coocc_render_eval_ssim(const float* rgbs, const float* gt_img, int N, int H, int W, double data_range, double* block,
+                               void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- LiDAR producer */
 /* Hard voxelisation (mmdet3d/ops/voxel/src/voxelization_cpu.cpp:44-104 = the deterministic CUDA path of
