@@ -27,6 +27,8 @@ from . import lidar
 from .lidar import HardSimpleVFE, SparseLiDAREnc4x, SparseLiDAREnc8x, Voxelization
 from . import lidar_hd
 from .lidar_hd import SparseEncoderHD
+from . import depth_net
+from .depth_net import DepthNet
 from .evaluation import SemanticEvaluator, cm_to_ious, evaluation_semantic
 
 register_into_mmdet()

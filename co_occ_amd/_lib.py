@@ -190,6 +190,12 @@ SIGNATURES = {
     "coocc_occ_loss_ws": (Z, [L, I]),
     "coocc_occ_loss_fwd": (I, [P, L, I, I, P, P, I, I, I, P, P, I, P, P, P, P, Z, P]),
     "coocc_occ_loss_bwd": (I, [P, L, I, I, P, P, I, P, P, P, P, I, P]),
+    "coocc_nbr_table2d": (I, [I, I, I, I, P, P]),
+    "coocc_dcn_cols": (I, [P, I, P, I, I, I, I, I, I, I, I, P, P]),
+    "coocc_se_gate2": (I, [P, I, I, I, I, P, P, P, P, P]),
+    "coocc_cam_mean_ws": (Z, [I, I, I]),
+    "coocc_cam_mean": (I, [P, I, I, I, I, P, P, Z, P]),
+    "coocc_cam_bias_relu": (I, [P, I, I, I, I, P, I, P]),
 }
 
 _lib = None

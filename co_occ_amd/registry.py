@@ -74,7 +74,7 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
 
 
 def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False,
-                        device_occ_losses=False):
+                        device_occ_losses=False, hip_depth_net=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -88,7 +88,10 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     ``SparseEncoderHD`` whose ``train_enabled`` is on, so the reference's own detector trains it under ``train()``; with
     ``detectors=True`` our ``COOCC_Ray_L`` is registered with the option on by default as well.  ``device_occ_losses=True`` (with
     ``detectors=True``) registers ``COOCC_Ray`` and ``COOCC_Ray_L`` with their ``device_occ_losses`` option on by default: OccHead's
-    loss terms and their gradient are computed on the device.  Returns False when mmdet / mmdet3d are not importable."""
+    loss terms and their gradient are computed on the device.  ``hip_depth_net=True`` registers a
+    ``ViewTransformerLiftSplatShootVoxel`` whose ``depth_net`` option defaults to ``'hip'``: an unchanged config then runs DepthNet on
+    the HIP engine (``depth_net.DepthNet``, inference) instead of the reference's class and mmcv's DCN.  Returns False when mmdet /
+    mmdet3d are not importable."""
     if device_occ_losses and not detectors:
         raise ValueError("register_into_mmdet: device_occ_losses=True is an option of this package's detectors; pass detectors=True")
     if train_lidar_trunk and not detectors:
@@ -114,6 +117,8 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
             theirs.register_module(name=k, force=True, module=cls)
     if train_sparse_encoder_hd:
         m3b.MIDDLE_ENCODERS.register_module(name="SparseEncoderHD", force=True, module=training_sparse_encoder_hd())
+    if hip_depth_net:
+        m3b.NECKS.register_module(name="ViewTransformerLiftSplatShootVoxel", force=True, module=hip_depth_net_view_transformer())
     if detectors and (train_lidar_trunk or train_sparse_encoder_hd):
         mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True,
                                      module=trunk_training_detector(train_lidar_trunk, train_sparse_encoder_hd))
@@ -147,6 +152,18 @@ def trunk_training_detector(train_lidar_trunk=True, train_sparse_encoder_hd=Fals
             super().__init__(*args, train_lidar_trunk=train_lidar_trunk, train_sparse_encoder_hd=train_sparse_encoder_hd, **kwargs)
     COOCC_Ray_L.__qualname__ = "COOCC_Ray_L"
     return COOCC_Ray_L
+
+
+def hip_depth_net_view_transformer():
+    """``ViewTransformerLiftSplatShootVoxel`` whose ``depth_net`` option defaults to ``'hip'`` (what
+    ``register_into_mmdet(hip_depth_net=True)`` puts into mmdet3d's registry under the reference name)."""
+    base = NECKS.get("ViewTransformerLiftSplatShootVoxel")
+
+    class ViewTransformerLiftSplatShootVoxel(base):
+        def __init__(self, *args, depth_net='hip', **kwargs):
+            super().__init__(*args, depth_net=depth_net, **kwargs)
+    ViewTransformerLiftSplatShootVoxel.__qualname__ = "ViewTransformerLiftSplatShootVoxel"
+    return ViewTransformerLiftSplatShootVoxel
 
 
 def training_sparse_encoder_hd():

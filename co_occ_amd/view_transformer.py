@@ -1,8 +1,9 @@
 """``ViewTransformerLiftSplatShootVoxel`` -- P/coocc/image2bev/ViewTransformerLSSVoxel.py /
 ViewTransformerLSSBEVDepth.py: geometry (P1), voxel pooling (P2), and ``forward`` with the reference signature where
 Lift (x) Splat is ONE fused HIP pass (the [B,N,D,H,W,C] volume is never materialised).
-DepthNet (DCN + ASPP, the image branch upstream of the path) is not re-implemented: ``depth_net`` is the
-reference's own class when the plugin is importable, or an injected nn.Module.
+DepthNet (DCN + ASPP, the image branch upstream of the path): ``depth_net='hip'`` builds this package's
+``depth_net.DepthNet`` (HIP engine, inference); otherwise ``depth_net`` is an injected nn.Module, else the reference's own class
+when the plugin and mmcv's DCN are importable.
 """
 import torch
 from torch import nn
@@ -94,7 +95,14 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         self.frustum = self.create_frustum()
         self.D = self.frustum.shape[0]
         self.cam_channels = cam_channels
-        self.depth_net = depth_net if isinstance(depth_net, nn.Module) else self._reference_depth_net()
+        if isinstance(depth_net, nn.Module):
+            self.depth_net = depth_net
+        elif isinstance(depth_net, str) and depth_net == 'hip':
+            # opt-in: DepthNet(numC_input, numC_input, numC_Trans, D, cam_channels) of ViewTransformerLSSBEVDepth.py:616-617 on the HIP engine
+            from .depth_net import DepthNet
+            self.depth_net = DepthNet(self.numC_input, self.numC_input, self.numC_Trans, self.D, cam_channels=self.cam_channels)
+        else:
+            self.depth_net = self._reference_depth_net()
 
     def _reference_depth_net(self):
         """DepthNet(numC_input, numC_input, numC_Trans, D, cam_channels) of ViewTransformerLSSBEVDepth.py:616-617 -- the
@@ -266,7 +274,7 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         x = input[0]
         if self.depth_net is None:
             raise NotImplementedError("ViewTransformerLiftSplatShootVoxel.lift: DepthNet is upstream of the hot path and "
-                                      "could not be built here (needs the reference plugin + mmcv DCN); pass depth_net=<module>")
+                                      "could not be built here (needs the reference plugin + mmcv DCN); pass depth_net='hip' or depth_net=<module>")
         B, N, C, H, W = x.shape
         y = self.depth_net(x.view(B * N, C, H, W), input[7])
         return self.get_depth_dist(y[:, :self.D, ...]), y[:, self.D:self.D + self.numC_Trans, ...]
@@ -288,7 +296,7 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             return self.voxel_pooling(geom, x), geom
         if self.depth_net is None:
             raise NotImplementedError("ViewTransformerLiftSplatShootVoxel.forward: DepthNet is upstream of the hot path and "
-                                      "could not be built here (needs the reference plugin + mmcv DCN); pass depth_net=<module>")
+                                      "could not be built here (needs the reference plugin + mmcv DCN); pass depth_net='hip' or depth_net=<module>")
         B, N, C, H, W = x.shape
         y = self.depth_net(x.view(B * N, C, H, W), input[7])
         depth_prob = self.get_depth_dist(y[:, :self.D, ...])

@@ -924,6 +924,28 @@ int coocc_occ_loss_fwd(const float* logits, int64_t P, int C, int ld, const uint
 int coocc_occ_loss_bwd(const float* logits, int64_t P, int C, int ld, const uint8_t* row_labels, const float* class_w, int empty_idx,
                        const double* stats, const float* lov_w, const float* gout, float* dlogits, int ldg, void* stream);
 
+/* ---- DepthNet (co_occ_amd/depth_net.py, csrc/depthnet.hip).  Feature maps are rows [BN*H*W][C], row (b*H + y)*W + x. */
+/* Row table of a 3x3 convolution with dilation = padding = dil on BN maps of H x W: table[3i + j][m] = the row of
+ * (y + (i-1) dil, x + (j-1) dil) of the SAME map, or -1 in the padding.  table:[9][BN*H*W], every entry written. */
+int coocc_nbr_table2d(int BN, int H, int W, int dil, int32_t* table, void* stream);
+/* Deformable sampler of DCNv1 (3x3, padding 1, deform_groups 1) for rows [m0, m0 + n): off [BN*H*W][off_stride] holds (dy, dx) of tap
+ * t = 3i + j at columns 2t, 2t + 1; the sample of tap t at pixel (y, x) is x bilinearly at (y - 1 + i + dy, x - 1 + j + dx), 0 when
+ * the position is <= -1 or >= H (W), corners outside the map contribute 0.  cols: `groups` matrices [n][9 * C/groups] one after the
+ * other, column t * C/groups + c of group g = channel g * C/groups + c.  (C/groups) % 4 == 0, x_stride % 4 == 0, 16-byte aligned x,
+ * cols.  A map's taps never read another map's rows. */
+int coocc_dcn_cols(const float* x, int x_stride, const float* off, int off_stride, int BN, int H, int W, int C, int groups, int m0,
+                   int n, float* cols, void* stream);
+/* out_a = x * sigmoid(gate_a[camera]), out_b = x * sigmoid(gate_b[camera]) in one pass over x [BN*rows_per_cam][x_stride]; gates
+ * [BN][C] (logits), outputs [BN*rows_per_cam][C].  C % 4 == 0, 16-byte aligned pointers. */
+int coocc_se_gate2(const float* x, int x_stride, int BN, int rows_per_cam, int C, const float* gate_a, const float* gate_b,
+                   float* out_a, float* out_b, void* stream);
+/* Bytes of workspace coocc_cam_mean needs. */
+size_t coocc_cam_mean_ws(int BN, int HW, int C);
+/* mean[b][c] over the HW rows of camera b of x [BN*HW][stride]: fp64 sums in a fixed order (deterministic). */
+int coocc_cam_mean(const float* x, int stride, int BN, int HW, int C, float* mean, void* ws, size_t ws_bytes, void* stream);
+/* y = y + bias[camera] (then ReLU when `relu`) in place on y [BN*rows_per_cam][y_stride], bias [BN][C].  C % 4 == 0, 16-byte aligned. */
+int coocc_cam_bias_relu(float* y, int y_stride, int BN, int rows_per_cam, int C, const float* bias, int relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
