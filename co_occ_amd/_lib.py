@@ -196,6 +196,12 @@ SIGNATURES = {
     "coocc_cam_mean_ws": (Z, [I, I, I]),
     "coocc_cam_mean": (I, [P, I, I, I, I, P, P, Z, P]),
     "coocc_cam_bias_relu": (I, [P, I, I, I, I, P, I, P]),
+    "coocc_dcn_cols_bwd": (I, [P, I, P, I, I, I, I, I, I, I, I, P, P, P, P]),
+    "coocc_se_gate2_bwd_ws": (Z, [I, I, I]),
+    "coocc_se_gate2_bwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, Z, P]),
+    "coocc_cam_sum": (I, [P, I, I, I, I, P, P, Z, P]),
+    "coocc_cam_add": (I, [P, P, I, I, I, P, F, P]),
+    "coocc_dropout_rows": (I, [P, P, L, I, F, P, P]),
 }
 
 _lib = None

@@ -74,7 +74,7 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
 
 
 def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False,
-                        device_occ_losses=False, hip_depth_net=False):
+                        device_occ_losses=False, hip_depth_net=False, train_depth_net=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -90,8 +90,11 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     ``detectors=True``) registers ``COOCC_Ray`` and ``COOCC_Ray_L`` with their ``device_occ_losses`` option on by default: OccHead's
     loss terms and their gradient are computed on the device.  ``hip_depth_net=True`` registers a
     ``ViewTransformerLiftSplatShootVoxel`` whose ``depth_net`` option defaults to ``'hip'``: an unchanged config then runs DepthNet on
-    the HIP engine (``depth_net.DepthNet``, inference) instead of the reference's class and mmcv's DCN.  Returns False when mmdet /
-    mmdet3d are not importable."""
+    the HIP engine (``depth_net.DepthNet``) instead of the reference's class and mmcv's DCN; ``train_depth_net=True`` (with
+    ``hip_depth_net=True``) registers it with its ``train_depth_net`` option on by default as well, so the module also trains on the
+    HIP engine under ``train()``.  Returns False when mmdet / mmdet3d are not importable."""
+    if train_depth_net and not hip_depth_net:
+        raise ValueError("register_into_mmdet: train_depth_net=True trains this package's DepthNet; pass hip_depth_net=True")
     if device_occ_losses and not detectors:
         raise ValueError("register_into_mmdet: device_occ_losses=True is an option of this package's detectors; pass detectors=True")
     if train_lidar_trunk and not detectors:
@@ -118,7 +121,7 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     if train_sparse_encoder_hd:
         m3b.MIDDLE_ENCODERS.register_module(name="SparseEncoderHD", force=True, module=training_sparse_encoder_hd())
     if hip_depth_net:
-        m3b.NECKS.register_module(name="ViewTransformerLiftSplatShootVoxel", force=True, module=hip_depth_net_view_transformer())
+        m3b.NECKS.register_module(name="ViewTransformerLiftSplatShootVoxel", force=True, module=hip_depth_net_view_transformer(train_depth_net))
     if detectors and (train_lidar_trunk or train_sparse_encoder_hd):
         mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True,
                                      module=trunk_training_detector(train_lidar_trunk, train_sparse_encoder_hd))
@@ -154,14 +157,16 @@ def trunk_training_detector(train_lidar_trunk=True, train_sparse_encoder_hd=Fals
     return COOCC_Ray_L
 
 
-def hip_depth_net_view_transformer():
-    """``ViewTransformerLiftSplatShootVoxel`` whose ``depth_net`` option defaults to ``'hip'`` (what
-    ``register_into_mmdet(hip_depth_net=True)`` puts into mmdet3d's registry under the reference name)."""
+def hip_depth_net_view_transformer(train_depth_net=False):
+    """``ViewTransformerLiftSplatShootVoxel`` whose ``depth_net`` option defaults to ``'hip'`` and whose ``train_depth_net`` option
+    defaults to the given value (what ``register_into_mmdet(hip_depth_net=True)`` puts into mmdet3d's registry under the reference
+    name)."""
     base = NECKS.get("ViewTransformerLiftSplatShootVoxel")
+    train_default = bool(train_depth_net)
 
     class ViewTransformerLiftSplatShootVoxel(base):
-        def __init__(self, *args, depth_net='hip', **kwargs):
-            super().__init__(*args, depth_net=depth_net, **kwargs)
+        def __init__(self, *args, depth_net='hip', train_depth_net=train_default, **kwargs):
+            super().__init__(*args, depth_net=depth_net, train_depth_net=train_depth_net, **kwargs)
     ViewTransformerLiftSplatShootVoxel.__qualname__ = "ViewTransformerLiftSplatShootVoxel"
     return ViewTransformerLiftSplatShootVoxel
 

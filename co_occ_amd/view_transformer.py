@@ -2,7 +2,7 @@
 ViewTransformerLSSBEVDepth.py: geometry (P1), voxel pooling (P2), and ``forward`` with the reference signature where
 Lift (x) Splat is ONE fused HIP pass (the [B,N,D,H,W,C] volume is never materialised).
 DepthNet (DCN + ASPP, the image branch upstream of the path): ``depth_net='hip'`` builds this package's
-``depth_net.DepthNet`` (HIP engine, inference); otherwise ``depth_net`` is an injected nn.Module, else the reference's own class
+``depth_net.DepthNet`` (HIP engine; ``train_depth_net=True`` also builds its training path); otherwise ``depth_net`` is an injected nn.Module, else the reference's own class
 when the plugin and mmcv's DCN are importable.
 """
 import torch
@@ -72,7 +72,7 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
     def __init__(self, loss_depth_weight=1.0, scale=16, point_cloud_range=None, loss_depth_type='bce',
                  grid_config=None, data_config=None, numC_input=512, numC_Trans=64, downsample=16,
                  accelerate=False, use_bev_pool=True, vp_megvii=False, vp_stero=False, cam_channels=27,
-                 loss_depth_reg_weight=0.0, use_voxel_net=False, depth_net=None, **kwargs):
+                 loss_depth_reg_weight=0.0, use_voxel_net=False, depth_net=None, train_depth_net=False, **kwargs):
         super().__init__()
         if use_voxel_net:
             raise NotImplementedError("DepthAggregation (use_voxel_net) is not used by the coocc_nusc configs")
@@ -101,8 +101,12 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
             # opt-in: DepthNet(numC_input, numC_input, numC_Trans, D, cam_channels) of ViewTransformerLSSBEVDepth.py:616-617 on the HIP engine
             from .depth_net import DepthNet
             self.depth_net = DepthNet(self.numC_input, self.numC_input, self.numC_Trans, self.D, cam_channels=self.cam_channels)
+            # opt-in: under train() DepthNet runs its differentiable forward on the HIP engine (off: train() raises)
+            self.depth_net.train_enabled = bool(train_depth_net)
         else:
             self.depth_net = self._reference_depth_net()
+        if train_depth_net and not (isinstance(depth_net, str) and depth_net == 'hip'):
+            raise ValueError("ViewTransformerLiftSplatShootVoxel: train_depth_net=True trains this package's DepthNet; pass depth_net='hip'")
 
     def _reference_depth_net(self):
         """DepthNet(numC_input, numC_input, numC_Trans, D, cam_channels) of ViewTransformerLSSBEVDepth.py:616-617 -- the

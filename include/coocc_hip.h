@@ -946,6 +946,30 @@ int coocc_cam_mean(const float* x, int stride, int BN, int HW, int C, float* mea
 /* y = y + bias[camera] (then ReLU when `relu`) in place on y [BN*rows_per_cam][y_stride], bias [BN][C].  C % 4 == 0, 16-byte aligned. */
 int coocc_cam_bias_relu(float* y, int y_stride, int BN, int rows_per_cam, int C, const float* bias, int relu, void* stream);
 
+/* ---- DepthNet training (DepthNet.train_enabled). */
+/* Adjoint of coocc_dcn_cols over the rows [m0, m0 + n): dcols as coocc_dcn_cols writes cols.  dx [BN*H*W][C] (dense, ZEROED BY THE
+ * CALLER, shared by every chunk) += w_corner * dcol by fp32 atomic adds -- the summation order, hence the last bits, may differ from
+ * run to run.  doff [n][off_stride]: columns 2t / 2t + 1 = d/dy, d/dx of tap t: sum_c dcol_c (hx (x10 - x00) + lx (x11 - x01)) and
+ * sum_c dcol_c (hy (x01 - x00) + ly (x11 - x10)) with corners outside the map read as 0 -- the derivative of the floor-based
+ * four-corner form (the right derivative at integer positions), 0 when the position is <= -1 or >= H (W) or not a number; columns
+ * from 18 up are 0.  doff is deterministic (per-lane fp32 partials, fixed-order wave reduction, no atomics). */
+int coocc_dcn_cols_bwd(const float* x, int x_stride, const float* off, int off_stride, int BN, int H, int W, int C, int groups,
+                       int m0, int n, const float* dcols, float* dx, float* doff, void* stream);
+/* Bytes of workspace coocc_se_gate2_bwd needs. */
+size_t coocc_se_gate2_bwd_ws(int BN, int HW, int C);
+/* Backward of coocc_se_gate2: dx = d_out_a sigmoid(gate_a[camera]) + d_out_b sigmoid(gate_b[camera]) [BN*rows_per_cam][C];
+ * dgate_a[b][c] = sigmoid'(gate_a[b][c]) sum over camera b's rows of x d_out_a, likewise dgate_b: fp64 sums in a fixed order. */
+int coocc_se_gate2_bwd(const float* x, int x_stride, int BN, int rows_per_cam, int C, const float* gate_a, const float* gate_b,
+                       const float* d_out_a, const float* d_out_b, float* dx, float* dgate_a, float* dgate_b, void* ws,
+                       size_t ws_bytes, void* stream);
+/* sum[b][c] over the HW rows of camera b (coocc_cam_mean without the division; same workspace): the adjoint of coocc_cam_add in v. */
+int coocc_cam_sum(const float* x, int stride, int BN, int HW, int C, float* sum, void* ws, size_t ws_bytes, void* stream);
+/* y = x + v[camera] * scale on dense rows [BN*rows_per_cam][C] (x NULL: y = v[camera] * scale, the adjoint of coocc_cam_mean with
+ * scale = 1 / HW; x == y is allowed).  C % 4 == 0, 16-byte aligned. */
+int coocc_cam_add(const float* x, float* y, int BN, int rows_per_cam, int C, const float* v, float scale, void* stream);
+/* y = x * mask * scale on dense rows [M][C], mask [M][C] bytes of 0 / 1 (scale = 1 / (1 - p)); the backward is the same call on dy. */
+int coocc_dropout_rows(const float* x, const uint8_t* mask, int64_t M, int C, float scale, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
