@@ -202,6 +202,7 @@ SIGNATURES = {
     "coocc_cam_sum": (I, [P, I, I, I, I, P, P, Z, P]),
     "coocc_cam_add": (I, [P, P, I, I, I, P, F, P]),
     "coocc_dropout_rows": (I, [P, P, L, I, F, P, P]),
+    "coocc_img_stem": (I, [P, I, I, I, P, P, P, I, I, I, P, I, P, P]),
 }
 
 _lib = None

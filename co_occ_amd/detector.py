@@ -15,7 +15,9 @@ pts_bbox_head.* / sigma_head.* / rgb_head.*`` entries load unchanged.
 UPSTREAM of the hot path (out of scope) and are NOT re-implemented: they are built through the real
 mmdet / mmdet3d registries when those packages are importable, may be injected as ``nn.Module`` instances, and
 otherwise construction fails (``external_encoders=True`` defers the failure to the first call that needs them, for
-callers that feed ``precomputed=`` features or attach the encoders afterwards).
+callers that feed ``precomputed=`` features or attach the encoders afterwards).  Opt-in exceptions: ``hip_image_encoder=True``
+builds ResNet / SECONDFPN config dicts from ``image_encoder`` (HIP engine, inference only), ``depth_net='hip'`` on the view
+transformer builds ``depth_net.DepthNet``.
 """
 import numpy as np
 import torch
@@ -28,11 +30,17 @@ from .render import MLP, render_block, render_losses
 from .view_transformer import get_frustum
 
 
-def _build_upstream(kind, cfg, external):
+def _build_upstream(kind, cfg, external, hip_image=False):
     """``img_backbone`` / ``img_neck`` / ``pts_backbone`` / ``pts_neck``: modules upstream of the hot path.  Resolution
-    order: an injected nn.Module -> our registries (a type we do implement) -> the real mmdet3d builder -> error."""
+    order: an injected nn.Module -> (``hip_image``: the image encoder's own registries, for a config dict of type ResNet /
+    SECONDFPN) -> our registries (a type we do implement) -> the real mmdet3d builder -> error."""
     if cfg is None or isinstance(cfg, nn.Module):
         return cfg
+    if hip_image:
+        from . import image_encoder
+        mine = {"backbone": (image_encoder.IMAGE_BACKBONES, "ResNet"), "neck": (image_encoder.IMAGE_NECKS, "SECONDFPN")}[kind]
+        if cfg.get("type") == mine[1]:
+            return mine[0].build(cfg)
     ours = {"backbone": registry.BACKBONES, "neck": registry.NECKS}[kind]
     if cfg.get("type") in ours:
         return ours.build(cfg)
@@ -104,7 +112,8 @@ class COOCC_Ray(nn.Module):
                  test_rendering=False, img_view_transformer=None, pts_bbox_head=None, pts_voxel_layer=None,
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
-                 train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, render_ssim=False, **kwargs):
+                 train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, render_ssim=False, hip_image_encoder=False,
+                 **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -139,8 +148,15 @@ class COOCC_Ray(nn.Module):
                 raise NotImplementedError("COOCC_Ray: pts_middle_encoder type %r is not on the MI355X path (SparseLiDAREnc8x / "
                                           "SparseLiDAREnc4x are); pass external_encoders=True to attach it yourself"
                                           % pts_middle_encoder.get("type"))
-        self.img_backbone = _build_upstream("backbone", img_backbone, external_encoders)
-        self.img_neck = _build_upstream("neck", img_neck, external_encoders)
+        # opt-in: ``img_backbone`` / ``img_neck`` config dicts of type ResNet / SECONDFPN are built from ``image_encoder`` -- the HIP
+        # engine, inference only -- instead of staying upstream (mmdet / mmdet3d); module instances are taken as they are
+        self.hip_image_encoder = bool(hip_image_encoder)
+        self.img_backbone = _build_upstream("backbone", img_backbone, external_encoders, self.hip_image_encoder)
+        self.img_neck = _build_upstream("neck", img_neck, external_encoders, self.hip_image_encoder)
+        if self.hip_image_encoder:
+            from . import image_encoder
+            if isinstance(self.img_backbone, image_encoder.ResNet) and isinstance(self.img_neck, image_encoder.SECONDFPN):
+                self.img_backbone.output_readers = image_encoder.NeckReaders(self.img_neck)
         self.pts_backbone = _build_upstream("backbone", pts_backbone, external_encoders)
         self.pts_neck = _build_upstream("neck", pts_neck, external_encoders)
         self.empty_idx, self.scale = empty_idx, scale

@@ -74,7 +74,7 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
 
 
 def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False,
-                        device_occ_losses=False, hip_depth_net=False, train_depth_net=False):
+                        device_occ_losses=False, hip_depth_net=False, train_depth_net=False, hip_image_encoder=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -92,7 +92,9 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     ``ViewTransformerLiftSplatShootVoxel`` whose ``depth_net`` option defaults to ``'hip'``: an unchanged config then runs DepthNet on
     the HIP engine (``depth_net.DepthNet``) instead of the reference's class and mmcv's DCN; ``train_depth_net=True`` (with
     ``hip_depth_net=True``) registers it with its ``train_depth_net`` option on by default as well, so the module also trains on the
-    HIP engine under ``train()``.  Returns False when mmdet / mmdet3d are not importable."""
+    HIP engine under ``train()``.  ``hip_image_encoder=True`` registers ``image_encoder.ResNet`` / ``image_encoder.SECONDFPN`` (the 2-D
+    image backbone and neck on the HIP engine, inference only) under the reference names ``ResNet`` / ``SECONDFPN``, so an unchanged
+    config builds them as ``img_backbone`` / ``img_neck``.  Returns False when mmdet / mmdet3d are not importable."""
     if train_depth_net and not hip_depth_net:
         raise ValueError("register_into_mmdet: train_depth_net=True trains this package's DepthNet; pass hip_depth_net=True")
     if device_occ_losses and not detectors:
@@ -122,6 +124,10 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
         m3b.MIDDLE_ENCODERS.register_module(name="SparseEncoderHD", force=True, module=training_sparse_encoder_hd())
     if hip_depth_net:
         m3b.NECKS.register_module(name="ViewTransformerLiftSplatShootVoxel", force=True, module=hip_depth_net_view_transformer(train_depth_net))
+    if hip_image_encoder:
+        from . import image_encoder
+        m3b.BACKBONES.register_module(name="ResNet", force=True, module=image_encoder.ResNet)
+        m3b.NECKS.register_module(name="SECONDFPN", force=True, module=image_encoder.SECONDFPN)
     if detectors and (train_lidar_trunk or train_sparse_encoder_hd):
         mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True,
                                      module=trunk_training_detector(train_lidar_trunk, train_sparse_encoder_hd))

@@ -970,6 +970,17 @@ int coocc_cam_add(const float* x, float* y, int BN, int rows_per_cam, int C, con
 /* y = x * mask * scale on dense rows [M][C], mask [M][C] bytes of 0 / 1 (scale = 1 / (1 - p)); the backward is the same call on dy. */
 int coocc_dropout_rows(const float* x, const uint8_t* mask, int64_t M, int C, float scale, float* y, void* stream);
 
+/* ---- image encoder (co_occ_amd/image_encoder.py, csrc/img_stem.hip) */
+/* The stem of the 2-D ResNet: Conv2d(3 -> C0, 7x7, stride 2, padding 3) + folded BN (+ ReLU) over img [BN][3][H][W] (fp32, contiguous
+ * NCHW, read directly), and with pool != 0 MaxPool2d(3, stride 2, padding 1) of that map fused behind it (the stride-2 map never
+ * reaches memory; padding is never a candidate of the maximum, whatever `relu` is).  w: [147][C0], row (ci*7 + ky)*7 + kx; scale /
+ * bias: [C0].  out: channels-last rows [BN*Ho*Wo][out_stride] (C0 channels), row (b*Ho + y)*Wo + x, with Hc = (H-1)/2 + 1,
+ * Wc = (W-1)/2 + 1 and (Ho, Wo) = (Hc, Wc) for pool == 0, ((Hc-1)/2 + 1, (Wc-1)/2 + 1) otherwise.  out_h2_twin: optional H2 copy
+ * [rows][C0] of the same rows (csrc/h2_rows.h).  fp32 fma in a fixed order (k ascending), no atomics: the same bits from run to run.
+ * C0 == 64; any H, W >= 1; BN*Hc*Wc < 2^31.  w / out / out_h2_twin 16-byte aligned, out_stride % 4 == 0. */
+int coocc_img_stem(const float* img, int BN, int H, int W, const float* w, const float* scale, const float* bias, int C0, int relu,
+                   int pool, float* out, int out_stride, void* out_h2_twin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
