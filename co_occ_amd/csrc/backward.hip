@@ -46,6 +46,7 @@ __global__ __launch_bounds__(256) void k_scatter_add_rows(const float* __restric
 extern "C" int coocc_scatter_add_rows(const float* src, int src_stride, const int32_t* idx, int n, int C, float* dst,
                                       int dst_stride, void* stream) {
   COOCC_CHECK_ARG(src && idx && dst && n >= 0 && C > 0, "scatter_add_rows: bad args");
+  COOCC_CHECK_ARG(src_stride >= C && dst_stride >= C, "scatter_add_rows: row strides below C");
   if (n == 0) return COOCC_OK;
   hipLaunchKernelGGL(k_scatter_add_rows, dim3(cdiv((long long)n * C, 256)), dim3(256), 0, as_stream(stream), src, src_stride,
                      idx, n, C, dst, dst_stride);
@@ -83,6 +84,9 @@ extern "C" int coocc_voxel_pool_bwd(const float* dout, int dout_stride, const fl
                                     int C, const float* lo_dx_host, int B, int X, int Y, int Z, float* dx, void* stream) {
   COOCC_CHECK_ARG(dout && geom && dx && lo_dx_host && npts > 0 && pts_per_batch > 0 && C > 0 && C % 4 == 0 && dout_stride % 4 == 0,
                   "voxel_pool_bwd: bad args");
+  COOCC_CHECK_ARG(dout_stride >= C && B > 0 && X > 0 && Y > 0 && Z > 0, "voxel_pool_bwd: dout_stride < C or an empty grid");
+  // the batch index p / pts_per_batch of the last point must stay inside the B gradient volumes
+  COOCC_CHECK_ARG((long long)npts <= (long long)B * pts_per_batch, "voxel_pool_bwd: more points than B * pts_per_batch");
   const float* l = lo_dx_host;
   hipLaunchKernelGGL(k_voxel_pool_bwd, dim3(cdiv((long long)npts * (C / 4), 256)), dim3(256), 0, as_stream(stream), dout,
                      dout_stride, geom, npts, pts_per_batch, C, l[0], l[1], l[2], l[3], l[4], l[5], X, Y, Z, dx);
@@ -131,6 +135,9 @@ extern "C" int coocc_lift_splat_bwd(const float* dout, int dout_stride, const fl
   COOCC_CHECK_ARG(dout && depth && feat_nhwc && geom && lo_dx_host && d_depth && d_feat_nhwc && N > 0 && D > 0 && H > 0 && W > 0,
                   "lift_splat_bwd: bad args");
   COOCC_CHECK_ARG(C > 0 && C % 4 == 0 && dout_stride % 4 == 0 && pts_per_batch > 0, "lift_splat_bwd: C, stride % 4 == 0");
+  COOCC_CHECK_ARG(dout_stride >= C && B > 0 && X > 0 && Y > 0 && Z > 0, "lift_splat_bwd: dout_stride < C or an empty grid");
+  // the batch index p / pts_per_batch of the last point must stay inside the B gradient volumes
+  COOCC_CHECK_ARG((long long)N * D * H * W <= (long long)B * pts_per_batch, "lift_splat_bwd: more points than B * pts_per_batch");
   const float* l = lo_dx_host;
   hipLaunchKernelGGL(k_lift_splat_bwd, dim3(cdiv((long long)N * H * W, 4)), dim3(256), 0, as_stream(stream), dout, dout_stride,
                      depth, feat_nhwc, geom, N, D, H * W, C, pts_per_batch, l[0], l[1], l[2], l[3], l[4], l[5], X, Y, Z, d_depth,
@@ -396,6 +403,7 @@ __global__ __launch_bounds__(256) void k_upsample_trilinear_bwd(const float* __r
 extern "C" int coocc_upsample_trilinear_bwd(const float* dfine, float* dcoarse, int B, int C, int Xc, int Yc, int Zc, int Xf,
                                             int Yf, int Zf, int accumulate, void* stream) {
   COOCC_CHECK_ARG(dfine && dcoarse && B > 0 && C > 0 && C % 4 == 0, "upsample_trilinear_bwd: bad args (C % 4 == 0)");
+  COOCC_CHECK_ARG(Xc > 0 && Yc > 0 && Zc > 0, "upsample_trilinear_bwd: empty coarse grid");
   COOCC_CHECK_ARG(Xf <= 8 * Xc && Yf <= 8 * Yc && Zf <= 8 * Zc && Xf >= Xc && Yf >= Yc && Zf >= Zc,
                   "upsample_trilinear_bwd: supports upsampling factors up to 8");
   hipLaunchKernelGGL(k_upsample_trilinear_bwd, dim3(cdiv((long long)B * Xc * Yc * Zc * (C / 4), 256)), dim3(256), 0,
@@ -458,6 +466,11 @@ extern "C" int coocc_occhead_mix_bwd(const float* const* levels_host, const int*
                                      const float* dout, float* const* glevels_host, float* dwlogit, int B, int C,
                                      void* stream) {
   COOCC_CHECK_ARG(levels_host && dims_host && dout && glevels_host && L >= 1 && L <= 4 && C % 4 == 0, "occhead_mix_bwd: bad args");
+  COOCC_CHECK_ARG(B > 0 && C > 0, "occhead_mix_bwd: B, C > 0");
+  for (int l = 0; l < L; ++l) {
+    COOCC_CHECK_ARG(levels_host[l] && glevels_host[l], "occhead_mix_bwd: null level or gradient pointer");
+    COOCC_CHECK_ARG(dims_host[l * 3] > 0 && dims_host[l * 3 + 1] > 0 && dims_host[l * 3 + 2] > 0, "occhead_mix_bwd: empty level");
+  }
   MixLevelsB lv;
   lv.L = L;
   for (int l = 0; l < 4; ++l) {
@@ -509,6 +522,10 @@ extern "C" int coocc_fine_sample_voxel_bwd(const float* dfeat, int dfeat_stride,
                                            const int64_t* fine_xyz, int64_t nfine, const int* final_size_host, float* dvol,
                                            void* stream) {
   COOCC_CHECK_ARG(dfeat && fine_xyz && final_size_host && dvol && C > 0 && nfine >= 0, "fine_sample_voxel_bwd: bad args");
+  COOCC_CHECK_ARG(dfeat_stride >= C && X > 0 && Y > 0 && Z > 0, "fine_sample_voxel_bwd: dfeat_stride < C or an empty volume");
+  // q / (final - 1) normalises the fine coordinate
+  COOCC_CHECK_ARG(final_size_host[0] >= 2 && final_size_host[1] >= 2 && final_size_host[2] >= 2,
+                  "fine_sample_voxel_bwd: final_size below 2");
   hipStream_t s = as_stream(stream);
   COOCC_HIP(hipMemsetAsync(dvol, 0, sizeof(float) * (size_t)X * Y * Z * C, s));
   if (nfine == 0) return COOCC_OK;
@@ -653,6 +670,7 @@ extern "C" int coocc_fine_sample_img_bwd(const float* dfeat, int dfeat_stride, i
                                          const float* params, const int64_t* fine_xyz, int64_t nfine, float* dimg,
                                          void* stream) {
   COOCC_CHECK_ARG(dfeat && params && fine_xyz && dimg && ncam > 0 && Ci > 0 && nfine >= 0, "fine_sample_img_bwd: bad args");
+  COOCC_CHECK_ARG(dfeat_stride >= Ci && Hf > 0 && Wf > 0, "fine_sample_img_bwd: dfeat_stride < Ci or an empty feature map");
   hipStream_t s = as_stream(stream);
   COOCC_HIP(hipMemsetAsync(dimg, 0, sizeof(float) * (size_t)ncam * Hf * Wf * Ci, s));
   if (nfine == 0) return COOCC_OK;

@@ -441,13 +441,14 @@ int coocc_conv_wgrad_h2t(const float* in, int in_rows, int in_stride, const floa
 
 /* ---- backward of the HBM-bound ops (torch autograd over eager index_put / cumprod / interpolate upstream) */
 /* dst[r] = src[idx[r]] (zeros for idx < 0) and its adjoint dst[idx[r]] += src[r] (fp32 atomics): the G1 row
- * gather of bifuser_n.py:138-169 and its feature gradient. */
+ * gather of bifuser_n.py:138-169 and its feature gradient.  scatter_add_rows: both strides >= C. */
 int coocc_gather_rows(const float* src, int src_stride, const int32_t* idx, int n, int C, float* dst,
                       int dst_stride, void* stream);
 int coocc_scatter_add_rows(const float* src, int src_stride, const int32_t* idx, int n, int C, float* dst,
                            int dst_stride, void* stream);
 /* voxel_pooling backward (bev_pool_grad_kernel, bev_pool_cuda.cu:61-84, without the sort):
- * dx[p] = dout[voxel(p)] for kept points, 0 otherwise.  dout: NDHWC rows; dx:[npts,C]. */
+ * dx[p] = dout[voxel(p)] for kept points, 0 otherwise.  dout: NDHWC rows (dout_stride >= C); dx:[npts,C].
+ * Point p belongs to batch p / pts_per_batch: npts <= B * pts_per_batch (refused otherwise, here and in coocc_lift_splat_bwd). */
 int coocc_voxel_pool_bwd(const float* dout, int dout_stride, const float* geom, int npts, int pts_per_batch,
                          int C, const float* lo_dx_host, int B, int X, int Y, int Z, float* dx, void* stream);
 /* coocc_lift_splat backward: d_depth[N,D,H,W] and d_feat_nhwc[N,H,W,C] in one deterministic pass. */
@@ -469,7 +470,7 @@ int coocc_render_losses_bwd(const float* rgbs, const float* depths, const float*
                             float* ddepths, void* stream);
 
 /* coocc_upsample_add_trilinear backward w.r.t. the coarse volume (the fine gradient passes through):
- * dcoarse (+)= adjoint-trilinear(dfine).  Upsampling factors up to 4 per axis. */
+ * dcoarse (+)= adjoint-trilinear(dfine).  Upsampling factors from 1 up to 8 per axis. */
 int coocc_upsample_trilinear_bwd(const float* dfine, float* dcoarse, int B, int C, int Xc, int Yc, int Zc, int Xf,
                                  int Yf, int Zf, int accumulate, void* stream);
 
@@ -479,7 +480,8 @@ int coocc_occhead_mix_bwd(const float* const* levels_host, const int* dims_host,
                           const float* dout, float* const* glevels_host, float* dwlogit, int B, int C,
                           void* stream);
 
-/* coocc_fine_sample_voxel backward: dvol:[X*Y*Z,C] (zeroed here) += trilinear weights * dfeat rows (fp32 atomics). */
+/* coocc_fine_sample_voxel backward: dvol:[X*Y*Z,C] (zeroed here) += trilinear weights * dfeat rows (fp32 atomics).
+ * dfeat_stride >= C; every component of final_size >= 2 (the coordinates are normalised by final - 1). */
 int coocc_fine_sample_voxel_bwd(const float* dfeat, int dfeat_stride, int C, int X, int Y, int Z,
                                 const int64_t* fine_xyz, int64_t nfine, const int* final_size_host, float* dvol,
                                 void* stream);
