@@ -2,7 +2,8 @@
 
 Scope: the differentiable ops of the hot path with frozen-statistics BN (eval-mode BN folded into a
 per-channel scale/shift, exactly as the forward does): Conv3d / Linear (+BN, ReLU, residual) on
-channels-last rows, the G1 row gather, voxel pooling / fused lift-splat, the R2 render composite and
+channels-last rows -- one Function, ``ConvRowsFn``, for every dense convolution, keyed by per-axis kernel / stride / padding
+triples (a cubic layer is the one whose triples are equal) --, the G1 row gather, voxel pooling / fused lift-splat, the R2 render composite and
 the FPN trilinear upsample-add.  Indices (FPS / ball / top-K / assignment, voxel keys) are
 non-differentiable, as upstream.  Every backward is a HIP kernel; nothing falls back to torch ops.
 """
@@ -48,14 +49,24 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
-def tap_table(dev, B, Xi, Yi, Zi, ksize, stride, pad, dgrad):
-    """[taps, M] int32 row table of a conv geometry (cached): forward reads / dgrad reads."""
-    key = (dev.index, B, Xi, Yi, Zi, ksize, stride, pad, bool(dgrad))
+def _triple(v):
+    """An int, or a per-axis (x, y, z) triple, as a triple of ints."""
+    return (int(v),) * 3 if isinstance(v, int) else tuple(int(a) for a in v)
+
+
+def _out_dims(dims, kernel, strides, pads):
+    return tuple(out_dim(n, k, s, p) for n, k, s, p in zip(dims, kernel, strides, pads))
+
+
+def tap_table(dev, B, Xi, Yi, Zi, kernel, strides, pads, dgrad):
+    """[taps, M] int32 row table of a conv geometry given by per-axis kernel / stride / padding triples (cached): forward reads /
+    dgrad reads, tap t = (dx*ky + dy)*kz + dz (coocc_conv_tap_table3)."""
+    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads, bool(dgrad))
     if key not in _tables:
-        Xo, Yo, Zo = (out_dim(n, ksize, stride, pad) for n in (Xi, Yi, Zi))
+        Xo, Yo, Zo = _out_dims((Xi, Yi, Zi), kernel, strides, pads)
         M = B * Xi * Yi * Zi if dgrad else B * Xo * Yo * Zo
-        t = torch.empty(ksize ** 3, M, dtype=torch.int32, device=dev)
-        call("coocc_conv_tap_table", B, Xi, Yi, Zi, Xo, Yo, Zo, ksize, stride, pad, int(bool(dgrad)), ptr(t))
+        t = torch.empty(kernel[0] * kernel[1] * kernel[2], M, dtype=torch.int32, device=dev)
+        call("coocc_conv_tap_table3", B, Xi, Yi, Zi, Xo, Yo, Zo, *kernel, *strides, *pads, int(bool(dgrad)), ptr(t))
         _tables[key] = t
     return _tables[key]
 
@@ -63,11 +74,11 @@ def tap_table(dev, B, Xi, Yi, Zi, ksize, stride, pad, dgrad):
 _live = {}
 
 
-def live_taps(dev, B, Xi, Yi, Zi, ksize, stride, pad):
+def live_taps(dev, B, Xi, Yi, Zi, kernel, strides, pads):
     """(indices of the taps that read at least one real voxel, their rows of the forward table), cached per geometry."""
-    key = (dev.index, B, Xi, Yi, Zi, ksize, stride, pad)
+    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads)
     if key not in _live:
-        tb = tap_table(dev, B, Xi, Yi, Zi, ksize, stride, pad, False)
+        tb = tap_table(dev, B, Xi, Yi, Zi, kernel, strides, pads, False)
         idx = torch.nonzero((tb >= 0).any(1)).flatten()
         _live[key] = (idx, tb[idx].contiguous())
     return _live[key]
@@ -76,18 +87,21 @@ def live_taps(dev, B, Xi, Yi, Zi, ksize, stride, pad):
 _classes = {}
 
 
-def dgrad_classes(dev, B, Xi, Yi, Zi, ksize, stride, pad):
-    """Strided dgrad by residue class: input voxels with the same (x, y, z) mod stride are reached through the same
+def dgrad_classes(dev, B, Xi, Yi, Zi, kernel, strides, pads):
+    """Strided dgrad by residue class: input voxels with the same (x mod sx, y mod sy, z mod sz) are reached through the same
     subset of taps (stride 2, k = 3: 1, 2, 4 or 8 of the 27), so each class is its own small row-table GEMM instead
     of 27 taps of which 7/8 of the table entries are empty.  -> list of (rows int32 [Mc], taps int64 [Tc], table
-    int32 [Tc, Mc]) over the non-empty classes, cached per geometry."""
-    key = (dev.index, B, Xi, Yi, Zi, ksize, stride, pad)
+    int32 [Tc, Mc]) over the non-empty classes, cached per geometry.  Stride 4 with a 3-wide kernel: the class x mod 4 == 2
+    (pad 1) is reached through no tap -- no output reads those voxels -- and is left out; their gradient is the zero the caller
+    initialised."""
+    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads)
     if key not in _classes:
-        tb = tap_table(dev, B, Xi, Yi, Zi, ksize, stride, pad, True)          # [taps, Mi]: output row or -1
+        tb = tap_table(dev, B, Xi, Yi, Zi, kernel, strides, pads, True)          # [taps, Mi]: output row or -1
+        sx, sy, sz = strides
         m = torch.arange(B * Xi * Yi * Zi, device=dev)
-        cls = (((m // (Yi * Zi)) % Xi % stride) * stride + (m // Zi) % Yi % stride) * stride + m % Zi % stride
+        cls = (((m // (Yi * Zi)) % Xi % sx) * sy + (m // Zi) % Yi % sy) * sz + m % Zi % sz
         out = []
-        for c in range(stride ** 3):
+        for c in range(sx * sy * sz):
             rows = torch.nonzero(cls == c).flatten()
             if rows.numel() == 0:
                 continue
@@ -227,79 +241,121 @@ def _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw, gscale=None):
     return True
 
 
-def _conv_launch(x2d, in_C, w_packed, out2d, Cout, taps, geom_in, geom_out, ksize, stride, pad, scale, shift, res2d, relu,
-                 table=None, tag="conv_fwd", out_rows=None, kdims=None, h2_alpha=None, alpha_dev=None):
-    """``h2_alpha``: x2d holds H2 rows (coocc_rows_to_h2, operand scale 1 / h2_alpha) and w_packed an H2 pack: split-f16 engine;
-    ``alpha_dev``: device word the accumulators are also multiplied by (the inverse of a device-chosen operand scale)."""
-    M = out_rows.shape[0] if out_rows is not None else out2d.shape[0]
-    d = conv_desc(x2d.device, in_=ptr(x2d), w=ptr(w_packed), out=ptr(out2d), scale=ptr(scale), bias=ptr(shift), res=ptr(res2d),
-                  gather=ptr(table, torch.int32), out_rows=ptr(out_rows, torch.int32), M=M, Cin=in_C, Cout=Cout, taps=taps,
-                  in_stride=x2d.shape[1], out_stride=out2d.shape[1], res_stride=res2d.shape[1] if res2d is not None else 0,
-                  B=geom_in[0], Xi=geom_in[1], Yi=geom_in[2], Zi=geom_in[3], Xo=geom_out[1], Yo=geom_out[2], Zo=geom_out[3],
-                  ksize=ksize, stride=stride, pad=pad, relu=int(relu), res_mode=1 if res2d is not None else 0, tile_hint=TILE_HINT)
-    if kdims is not None:
-        d.kx, d.ky, d.kz, d.px, d.py, d.pz = kdims
+def _launch(d, x2d, in_C, tag, h2_alpha, alpha_dev):
+    """coocc_conv_fwd of ``d`` over the rows x2d.  ``h2_alpha``: x2d holds H2 rows (coocc_rows_to_h2, operand scale 1 / h2_alpha)
+    and d.w an H2 pack: split-f16 engine; ``alpha_dev``: device word the accumulators are also multiplied by (the inverse of a
+    device-chosen operand scale)."""
     if h2_alpha is not None:
         d.in_stride, d.mfma_dtype, d.alpha, d.alpha_dev, tag = in_C, 3, float(h2_alpha), alpha_dev, "k_gemm_h2 " + tag
-    launch_conv(d, x2d.device, tag, 2.0 * M * in_C * Cout * taps)
+    launch_conv(d, x2d.device, tag, 2.0 * d.M * in_C * d.Cout * d.taps)
+
+
+def _conv_launch(x2d, in_C, w_packed, out2d, Cout, geom_in, geom_out, kernel, strides, pads, scale, shift, res2d, relu,
+                 tag="conv_fwd", h2_alpha=None, alpha_dev=None):
+    """A convolution over a grid: rows of ``geom_in`` -> rows of ``geom_out`` through the descriptor's per-axis fields."""
+    d = conv_desc(x2d.device, in_=ptr(x2d), w=ptr(w_packed), out=ptr(out2d), scale=ptr(scale), bias=ptr(shift), res=ptr(res2d),
+                  M=out2d.shape[0], Cin=in_C, Cout=Cout, taps=kernel[0] * kernel[1] * kernel[2], in_stride=x2d.shape[1],
+                  out_stride=out2d.shape[1], res_stride=res2d.shape[1] if res2d is not None else 0, B=geom_in[0], Xi=geom_in[1],
+                  Yi=geom_in[2], Zi=geom_in[3], Xo=geom_out[1], Yo=geom_out[2], Zo=geom_out[3], ksize=max(kernel), stride=max(strides),
+                  pad=max(pads), relu=int(relu), res_mode=1 if res2d is not None else 0, tile_hint=TILE_HINT)
+    (d.kx, d.ky, d.kz), (d.px, d.py, d.pz), (d.sx, d.sy, d.sz) = kernel, pads, strides
+    _launch(d, x2d, in_C, tag, h2_alpha, alpha_dev)
+
+
+def _table_launch(x2d, in_C, w_packed, out2d, Cout, table, scale=None, shift=None, res2d=None, relu=False, tag="sparse", out_rows=None,
+                  h2_alpha=None, alpha_dev=None):
+    """A row-table GEMM: out2d[o] (or out2d[out_rows[o]]) = epi(sum_t W_t . x2d[table[t][o]]) with ``table`` int32 [taps, M], -1 =
+    no row.  With a table coocc_conv_fwd reads no geometry but the number of input rows, stated as B * Xi * Yi * Zi."""
+    M = out_rows.shape[0] if out_rows is not None else out2d.shape[0]
+    d = conv_desc(x2d.device, in_=ptr(x2d), w=ptr(w_packed), out=ptr(out2d), scale=ptr(scale), bias=ptr(shift), res=ptr(res2d),
+                  gather=ptr(table, torch.int32), out_rows=ptr(out_rows, torch.int32), M=M, Cin=in_C, Cout=Cout, taps=table.shape[0],
+                  in_stride=x2d.shape[1], out_stride=out2d.shape[1], res_stride=res2d.shape[1] if res2d is not None else 0,
+                  B=1, Xi=x2d.shape[0], Yi=1, Zi=1, Xo=out2d.shape[0], Yo=1, Zo=1, ksize=1, stride=1, pad=0, relu=int(relu),
+                  res_mode=1 if res2d is not None else 0, tile_hint=TILE_HINT)
+    _launch(d, x2d, in_C, tag, h2_alpha, alpha_dev)
+
+
+_UNIT, _NOPAD = (1, 1, 1), (0, 0, 0)
+
+
+def _wino_layer(kernel, strides, pads):
+    """The layers the training Winograd kernels (forward, dgrad, wgrad) cover: 3x3x3, stride 1, pad 1."""
+    return kernel == (3, 3, 3) and strides == _UNIT and pads == _UNIT
+
+
+def _ztrim(Zin, Zout, kernel, strides, pads):
+    """``core.ztrim`` of a 3x3x3 layer with equal strides and pads: ((lo, hi), the launch's kernel, its pads) when z taps that
+    only read padding can be dropped (exact), else None."""
+    if kernel != (3, 3, 3) or len(set(strides)) != 1 or len(set(pads)) != 1:
+        return None
+    trim, kd = ztrim(Zin, Zout, strides[0], pads[0])
+    return None if trim is None else (trim, kd[:3], kd[3:])
 
 
 class ConvRowsFn(torch.autograd.Function):
-    """y = relu(scale * conv(x, W) + shift + res) on channels-last rows; scale/shift are constants
-    (folded eval-mode BN and/or the conv bias).  Differentiable in x, W, conv bias and res."""
+    """y = relu(scale * conv(x, W) + shift + res) on channels-last rows for a layer with per-axis ``kernel`` / ``strides`` / ``pads``
+    triples (as ``core.PackedConv`` describes them; a cubic layer has equal ones); weight [Cout,Cin,kx,ky,kz] (or [Cout,Cin] for one
+    tap); scale/shift are constants (folded eval-mode BN and/or the conv bias).  Differentiable in x, W, conv bias and res.
+    Routes by the triple: Winograd forward / dgrad / wgrad for 3x3x3 stride 1 pad 1, the z trim for 3x3x3 with equal strides and
+    pads, the split-f16 (KH2) weight gradient for one tap at unit strides, residue-class dgrad wherever a stride exceeds 1; direct
+    form otherwise (the one-z-tap Winograd form of inference is not extended to training: the device-side packs are 3x3x3 only)."""
 
     @staticmethod
-    def forward(ctx, x2d, weight, bias, res2d, scale, shift, geom, ksize, stride, pad, relu):
+    def forward(ctx, x2d, weight, bias, res2d, scale, shift, geom, kernel, strides, pads, relu):
         B, Xi, Yi, Zi = geom
         Cout, Cin = weight.shape[0], weight.shape[1]
-        taps = ksize ** 3
+        taps = kernel[0] * kernel[1] * kernel[2]
+        assert tuple(weight.shape[2:]) in (kernel, ()), "weight %s is not [Cout,Cin,%d,%d,%d]" % ((tuple(weight.shape),) + kernel)
         assert x2d.shape == (B * Xi * Yi * Zi, Cin) and x2d.is_contiguous() and Cin % 4 == 0
-        Xo, Yo, Zo = (out_dim(n, ksize, stride, pad) for n in (Xi, Yi, Zi))
-        geom_out = (B, Xo, Yo, Zo)
-        out = torch.empty(B * Xo * Yo * Zo, Cout, device=x2d.device, dtype=_F32)
+        geom_out = (B,) + _out_dims((Xi, Yi, Zi), kernel, strides, pads)
+        out = torch.empty(geom_out[0] * geom_out[1] * geom_out[2] * geom_out[3], Cout, device=x2d.device, dtype=_F32)
         eff_shift = shift
         if bias is not None:    # y = scale * (conv + b) + shift
             eff_shift = (bias.detach() * scale if scale is not None else bias.detach()) + (shift if shift is not None else 0)
             eff_shift = eff_shift.float().contiguous()
         w_ = weight.detach().float().contiguous()
-        if not (ksize == 3 and stride == 1 and pad == 1 and
+        if not (_wino_layer(kernel, strides, pads) and
                 _wino_train(x2d, geom, w_.view(Cout, Cin, 3, 3, 3), False, out, scale, eff_shift, res2d, relu)):
-            wsub, nt = w_.reshape(Cout, Cin, taps), taps
-            trim, kd = ztrim(Zi, Zo, stride, pad) if ksize == 3 else (None, None)
+            wsub, kd, pd = w_.view(Cout, Cin, taps), kernel, pads
+            trim = _ztrim(Zi, geom_out[3], kernel, strides, pads)
             if trim is not None:         # z taps that only read padding are dropped (exact)
-                wsub, nt = _z_taps(w_, *trim), 9 * kd[2]
+                wsub, kd, pd = _z_taps(w_, *trim[0]), trim[1], trim[2]
+            nt = kd[0] * kd[1] * kd[2]
             if _h2_direct(Cin, 2.0 * out.shape[0] * Cin * Cout * nt):
-                _conv_launch(_rows_h2(x2d, Cin), Cin, pack_weights_h2_dev(wsub, Cout, Cin, nt, 0), out, Cout, nt, geom, geom_out, ksize,
-                             stride, pad, scale, eff_shift, res2d, relu, kdims=kd, h2_alpha=1.0)
+                _conv_launch(_rows_h2(x2d, Cin), Cin, pack_weights_h2_dev(wsub, Cout, Cin, nt, 0), out, Cout, geom, geom_out, kd,
+                             strides, pd, scale, eff_shift, res2d, relu, h2_alpha=1.0)
             else:
-                wp = pack_weights_dev(wsub, Cout, Cin, nt, 0)
-                _conv_launch(x2d, Cin, wp, out, Cout, nt, geom, geom_out, ksize, stride, pad, scale, eff_shift, res2d, relu, kdims=kd)
+                _conv_launch(x2d, Cin, pack_weights_dev(wsub, Cout, Cin, nt, 0), out, Cout, geom, geom_out, kd, strides, pd, scale,
+                             eff_shift, res2d, relu)
         ctx.save_for_backward(x2d, weight, out, scale if scale is not None else torch.empty(0, device=x2d.device))
-        ctx.cfg = (geom, geom_out, ksize, stride, pad, relu, bias is not None, res2d is not None, scale is not None)
+        ctx.cfg = (geom, geom_out, kernel, strides, pads, relu, bias is not None, res2d is not None, scale is not None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
+        from . import core
         x2d, weight, out, scale = ctx.saved_tensors
-        geom, geom_out, ksize, stride, pad, relu, has_bias, has_res, has_scale = ctx.cfg
+        geom, geom_out, kernel, strides, pads, relu, has_bias, has_res, has_scale = ctx.cfg
         scale = scale if has_scale else None
         B, Xi, Yi, Zi = geom
         Cout, Cin = weight.shape[0], weight.shape[1]
-        taps = ksize ** 3
+        taps = kernel[0] * kernel[1] * kernel[2]
         Mo, Mi = out.shape[0], x2d.shape[0]
         dev = x2d.device
         dout = dout.float().contiguous()
         need_x, need_w, need_b, need_res = ctx.needs_input_grad[:4]
+        unit, wino3 = strides == _UNIT, _wino_layer(kernel, strides, pads)
         Cp = _pad4(Cout)
         dacc = torch.zeros(Mo, Cp, device=dev, dtype=_F32) if Cp != Cout else torch.empty(Mo, Cp, device=dev, dtype=_F32)
         dres = torch.empty(Mo, Cout, device=dev, dtype=_F32) if (has_res and need_res) else None
         dbias = torch.empty(Cout, device=dev, dtype=_F32) if (has_bias and need_b) else None
         ws = workspace(dev)
-        from . import core
-        # split-f16 dgrad: max |dacc| collected by the pass that writes dacc -> {scale, 1 / scale} on the device (see TRAIN_H2_DGRAD)
+        # split-f16 GEMMs that read dacc: max |dacc| collected by the pass that writes dacc -> {scale, 1 / scale} on the device (see
+        # TRAIN_H2_DGRAD).  Asked for by the stride-1 dgrad (its K is Cout) and by the layers whose weight gradient has a split-f16
+        # form (Winograd domain, one tap); no other layer collects an amax it would never read
         gscale = None
-        if (core.CONV_ENGINE == "h2" and Cp == Cout and stride == 1 and Cin % 4 == 0 and
-                ((TRAIN_H2_DGRAD and need_x and Cout % 32 == 0) or (TRAIN_H2_WGRAD and need_w))):
+        if (core.CONV_ENGINE == "h2" and Cp == Cout and unit and Cin % 4 == 0 and
+                ((TRAIN_H2_DGRAD and need_x and Cout % 32 == 0) or (TRAIN_H2_WGRAD and need_w and (wino3 or taps == 1)))):
             gscale = torch.empty(2, device=dev, dtype=_F32)
         gscale_d = gscale if (TRAIN_H2_DGRAD and Cout % 32 == 0) else None      # the dgrad GEMM's K is Cout
         call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cp,
@@ -308,39 +364,39 @@ class ConvRowsFn(torch.autograd.Function):
         if dbias is not None and scale is not None:
             dbias = dbias * scale
         dx = dw = None
+        w_ = weight.detach().float().contiguous()
+        w3 = w_.view(Cout, Cin, taps)
         if need_x:
             dx = torch.empty(Mi, Cin, device=dev, dtype=_F32)
-            w3 = weight.reshape(Cout, Cin, taps)
-            if (stride == 1 and ksize == 3 and pad == 1 and Cp == Cout and
-                    _wino_train(dacc, geom, weight.detach().float().contiguous().view(Cout, Cin, 3, 3, 3), True, dx, None, None,
-                                None, False, grad_scale=gscale_d)):
+            if wino3 and Cp == Cout and _wino_train(dacc, geom, w_.view(Cout, Cin, 3, 3, 3), True, dx, None, None, None, False,
+                                                    grad_scale=gscale_d):
                 pass
-            elif stride == 1:
-                wsub, nt, pd = w3, taps, ksize - 1 - pad
-                trim, kd = ztrim(geom_out[3], Zi, 1, pd) if ksize == 3 else (None, None)    # z taps of the flipped kernel that see real dy voxels
+            elif unit:
+                # dx = conv(dacc, W') with every tap axis flipped (pack mode 2 reverses the mixed-radix tap index = each axis) and
+                # pad' = k - 1 - pad per axis
+                wsub, kd, pd = w3, kernel, tuple(k - 1 - p for k, p in zip(kernel, pads))
+                trim = _ztrim(geom_out[3], Zi, kernel, strides, pd)      # z taps of the flipped kernel that see real dy voxels
                 if trim is not None:
-                    wsub, nt = _z_taps(weight.detach().float(), 2 - trim[1], 2 - trim[0]), 9 * kd[2]
+                    wsub, kd, pd = _z_taps(w_, 2 - trim[0][1], 2 - trim[0][0]), trim[1], trim[2]
+                nt = kd[0] * kd[1] * kd[2]
                 if gscale_d is not None and _h2_direct(Cout, 2.0 * Mi * Cin * Cout * nt):
                     # the gradient operand scaled by gscale[0] (chosen on the device), undone by the GEMM through gscale[1]
-                    _conv_launch(_rows_h2(dacc, Cout, gscale_d), Cout, pack_weights_h2_dev(wsub, Cout, Cin, nt, 2), dx, Cin,
-                                 nt, geom_out, geom, ksize, 1, pd, None, None, None, False, tag="conv_dgrad", kdims=kd,
-                                 h2_alpha=1.0, alpha_dev=ptr(gscale_d, offset=1))
+                    _conv_launch(_rows_h2(dacc, Cout, gscale_d), Cout, pack_weights_h2_dev(wsub, Cout, Cin, nt, 2), dx, Cin, geom_out,
+                                 geom, kd, strides, pd, None, None, None, False, tag="conv_dgrad", h2_alpha=1.0,
+                                 alpha_dev=ptr(gscale_d, offset=1))
                 else:
-                    wp = pack_weights_dev(wsub, Cout, Cin, nt, 2)
-                    _conv_launch(dacc, Cp, wp, dx, Cin, nt, geom_out, geom, ksize, 1, pd, None, None, None, False,
-                                 tag="conv_dgrad", kdims=kd)
+                    _conv_launch(dacc, Cp, pack_weights_dev(wsub, Cout, Cin, nt, 2), dx, Cin, geom_out, geom, kd, strides, pd, None,
+                                 None, None, False, tag="conv_dgrad")
             else:
                 dx.zero_()          # voxels no output reads (and classes without taps) get a zero gradient
-                for rows_c, taps_c, table_c in dgrad_classes(dev, B, Xi, Yi, Zi, ksize, stride, pad):
-                    wp = pack_weights_dev(w3.detach().index_select(2, taps_c), Cout, Cin, taps_c.numel(), 3)
-                    _conv_launch(dacc, Cp, wp, dx, Cin, taps_c.numel(), geom_out, geom, ksize, stride, pad, None, None, None,
-                                 False, table=table_c, tag="conv_dgrad", out_rows=rows_c)
+                for rows_c, taps_c, table_c in dgrad_classes(dev, B, Xi, Yi, Zi, kernel, strides, pads):
+                    wp = pack_weights_dev(w3.index_select(2, taps_c), Cout, Cin, taps_c.numel(), 3)
+                    _table_launch(dacc, Cp, wp, dx, Cin, table_c, tag="conv_dgrad", out_rows=rows_c)
         if need_w:
             dw = torch.empty(Cout, Cin, taps, device=dev, dtype=_F32)
-            if ksize == 3 and stride == 1 and pad == 1 and Cp == Cout and _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw,
-                                                                                        gscale if TRAIN_H2_WGRAD else None):
+            if wino3 and Cp == Cout and _wino_wgrad(x2d, dacc, geom, Cin, Cout, dw, gscale if TRAIN_H2_WGRAD else None):
                 pass
-            elif (TRAIN_H2_WGRAD and gscale is not None and taps == 1 and stride == 1
+            elif (TRAIN_H2_WGRAD and gscale is not None and taps == 1 and unit
                   and 2.0 * Mo * Cin * Cout >= core.H2_DIRECT_MIN_FLOPS):
                 # 1x1x1 / Linear: both operands voxel-major (KH2), the gradient with its device-chosen scale
                 Mp = -(-Mo // 16) * 16
@@ -350,8 +406,8 @@ class ConvRowsFn(torch.autograd.Function):
                     call("coocc_conv_wgrad_h2", ptr(xk), ptr(dk), Mp, Cin, Cout, 1.0, ptr(gscale, offset=1), ptr(dw), 0, ptr(ws),
                          ws.numel())
             else:
-                tb = tap_table(dev, B, Xi, Yi, Zi, ksize, stride, pad, False) if (taps > 1 or stride > 1) else None
-                live = live_taps(dev, B, Xi, Yi, Zi, ksize, stride, pad) if tb is not None else None
+                tb = tap_table(dev, B, Xi, Yi, Zi, kernel, strides, pads, False) if (taps > 1 or not unit) else None
+                live = live_taps(dev, B, Xi, Yi, Zi, kernel, strides, pads) if tb is not None else None
                 if live is not None and live[0].numel() < taps:
                     # thin grids (Z = 1, 2): taps that only ever read padding have a zero gradient -- skip their GEMMs
                     idx, tb_live = live
@@ -371,24 +427,24 @@ class ConvRowsFn(torch.autograd.Function):
 
 def conv3d_rows(x2d, weight, geom, bias=None, bn=None, stride=1, pad=None, relu=True, res2d=None):
     """Differentiable Conv3d(+eval BN)(+res)(+ReLU) on rows [B*X*Y*Z, Cin] -> ([B*Xo*Yo*Zo, Cout], out geom).
-    ``weight`` [Cout,Cin,k,k,k] (or [Cout,Cin] for a Linear / 1x1)."""
+    ``weight`` [Cout,Cin,kx,ky,kz] (any strides: a permuted view of a reference [.,.,kz,ky,kx] parameter keeps its gradient), or
+    [Cout,Cin] for a Linear / 1x1; ``stride`` / ``pad``: an int or a per-axis triple (``pad`` None: k // 2 per axis)."""
     from .core import fold_bn
-    ksize = weight.shape[2] if weight.dim() == 5 else 1
-    if pad is None:
-        pad = ksize // 2
+    kernel = tuple(weight.shape[2:]) if weight.dim() == 5 else _UNIT
+    strides = _triple(stride)
+    pads = _triple(pad) if pad is not None else tuple(k // 2 for k in kernel)
     scale = shift = None
     if bn is not None:
         s, b = fold_bn(bn, None)
         scale, shift = s.to(x2d.device).contiguous(), b.to(x2d.device).contiguous()
-    out = ConvRowsFn.apply(x2d.contiguous(), weight, bias, res2d, scale, shift, tuple(geom), ksize, stride, pad, relu)
-    B, X, Y, Z = geom
-    return out, (B, out_dim(X, ksize, stride, pad), out_dim(Y, ksize, stride, pad), out_dim(Z, ksize, stride, pad))
+    out = ConvRowsFn.apply(x2d.contiguous(), weight, bias, res2d, scale, shift, tuple(geom), kernel, strides, pads, relu)
+    return out, (geom[0],) + _out_dims(tuple(geom[1:]), kernel, strides, pads)
 
 
 def linear_rows(x2d, weight, bias=None, relu=False):
     """Differentiable nn.Linear (+ReLU) on rows through the same kernels."""
     n = x2d.shape[0]
-    return ConvRowsFn.apply(x2d.contiguous(), weight, bias, None, None, None, (1, n, 1, 1), 1, 1, 0, relu)
+    return ConvRowsFn.apply(x2d.contiguous(), weight, bias, None, None, None, (1, n, 1, 1), _UNIT, _UNIT, _NOPAD, relu)
 
 
 # ----------------------------------------------------------------------------- G1 gather
@@ -705,12 +761,13 @@ def ncdhw_from_rows(rows, geom):
     return rows.view(B, X, Y, Z, rows.shape[1]).permute(0, 4, 1, 2, 3)
 
 
-def conv_bn_rows(x2d, weight, geom, bn=None, bias=None, stride=1, pad=None, relu=True, res2d=None):
+def conv_bn_rows(x2d, weight, geom, bn=None, bias=None, stride=1, pad=None, relu=True, res2d=None, sync=None):
     """Conv3d -> BatchNorm (+res) -> ReLU on rows with the norm layer's OWN mode: a BN in training mode normalises with
-    batch (or SyncBN all-reduced) statistics and updates its running stats, as nn.BatchNorm3d / nn.SyncBatchNorm do under
-    model.train() upstream; a BN in eval mode is folded into the GEMM epilogue (frozen statistics)."""
+    batch (or SyncBN all-reduced, ``sync`` as ``_sync_group`` reads it) statistics and updates its running stats, as
+    nn.BatchNorm3d / nn.SyncBatchNorm do under model.train() upstream; a BN in eval mode is folded into the GEMM epilogue (frozen
+    statistics).  The kernel is ``weight.shape[2:]``; ``stride`` / ``pad`` as ``conv3d_rows`` takes them."""
     if bn is not None and bn.training:
-        return conv3d_bn_train_rows(x2d, weight, geom, bn, stride=stride, pad=pad, relu=relu, res2d=res2d, bias=bias)
+        return conv3d_bn_train_rows(x2d, weight, geom, bn, stride=stride, pad=pad, relu=relu, res2d=res2d, bias=bias, sync=sync)
     return conv3d_rows(x2d, weight, geom, bias=bias, bn=bn, stride=stride, pad=pad, relu=relu, res2d=res2d)
 
 
@@ -1061,197 +1118,9 @@ def conv3d_bn_train_rows(x2d, weight, geom, bn, stride=1, pad=None, relu=True, r
 
 
 # ----------------------------------------------------------------------------- LiDAR-only trunk (SECOND3D + SECOND3DFPN)
-# Training of lidar_trunk's modules.  The anisotropic layers (3x3x1 kernels, strides (s, s, 1), pads (1, 1, 0)) have a Function of
-# their own beside ConvRowsFn -- whose cubic routes stay as they are -- on the same kernels: coocc_conv_fwd through the descriptor's
-# per-axis fields, the same launch with flipped weights for the stride-1 dgrad, row-table launches per residue class for the strided
-# one, coocc_conv_wgrad over the live taps.  Direct form throughout: the one-z-tap Winograd form of inference is not extended to
-# training (the device-side Winograd packs are 3x3x3 only).
-_tables3, _live3, _classes3 = {}, {}, {}
-
-
-def out_dims3(dims, kernel, strides, pads):
-    return tuple(out_dim(n, k, s, p) for n, k, s, p in zip(dims, kernel, strides, pads))
-
-
-def tap_table3(dev, B, Xi, Yi, Zi, kernel, strides, pads, dgrad):
-    """``tap_table`` for per-axis kernel / stride / padding triples (coocc_conv_tap_table3), cached per geometry."""
-    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads, bool(dgrad))
-    if key not in _tables3:
-        Xo, Yo, Zo = out_dims3((Xi, Yi, Zi), kernel, strides, pads)
-        M = B * Xi * Yi * Zi if dgrad else B * Xo * Yo * Zo
-        t = torch.empty(kernel[0] * kernel[1] * kernel[2], M, dtype=torch.int32, device=dev)
-        call("coocc_conv_tap_table3", B, Xi, Yi, Zi, Xo, Yo, Zo, *kernel, *strides, *pads, int(bool(dgrad)), ptr(t))
-        _tables3[key] = t
-    return _tables3[key]
-
-
-def live_taps3(dev, B, Xi, Yi, Zi, kernel, strides, pads):
-    """``live_taps`` of the per-axis forward table."""
-    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads)
-    if key not in _live3:
-        tb = tap_table3(dev, B, Xi, Yi, Zi, kernel, strides, pads, False)
-        idx = torch.nonzero((tb >= 0).any(1)).flatten()
-        _live3[key] = (idx, tb[idx].contiguous())
-    return _live3[key]
-
-
-def dgrad_classes3(dev, B, Xi, Yi, Zi, kernel, strides, pads):
-    """``dgrad_classes`` over the residue classes of (x mod sx, y mod sy, z mod sz).  Stride 4 with a 3-wide kernel: the class
-    x mod 4 == 2 (pad 1) is reached through no tap -- no output reads those voxels -- and is left out; their gradient is the zero
-    the caller initialised."""
-    key = (dev.index, B, Xi, Yi, Zi, kernel, strides, pads)
-    if key not in _classes3:
-        tb = tap_table3(dev, B, Xi, Yi, Zi, kernel, strides, pads, True)          # [taps, Mi]: output row or -1
-        sx, sy, sz = strides
-        m = torch.arange(B * Xi * Yi * Zi, device=dev)
-        cls = (((m // (Yi * Zi)) % Xi % sx) * sy + (m // Zi) % Yi % sy) * sz + m % Zi % sz
-        out = []
-        for c in range(sx * sy * sz):
-            rows = torch.nonzero(cls == c).flatten()
-            if rows.numel() == 0:
-                continue
-            sub = tb[:, rows]
-            taps = torch.nonzero((sub >= 0).any(1)).flatten()
-            if taps.numel() == 0:
-                continue
-            out.append((rows.int().contiguous(), taps, sub[taps].contiguous()))
-        _classes3[key] = out
-    return _classes3[key]
-
-
-def _conv_launch3(x2d, in_C, w_packed, out2d, Cout, taps, geom_in, geom_out, kernel, strides, pads, scale, shift, relu, table=None,
-                  tag="conv_fwd", out_rows=None, h2_alpha=None, alpha_dev=None):
-    """``_conv_launch`` with the descriptor's per-axis kernel / padding / stride fields."""
-    M = out_rows.shape[0] if out_rows is not None else out2d.shape[0]
-    d = conv_desc(x2d.device, in_=ptr(x2d), w=ptr(w_packed), out=ptr(out2d), scale=ptr(scale), bias=ptr(shift),
-                  gather=ptr(table, torch.int32), out_rows=ptr(out_rows, torch.int32), M=M, Cin=in_C, Cout=Cout, taps=taps,
-                  in_stride=x2d.shape[1], out_stride=out2d.shape[1], B=geom_in[0], Xi=geom_in[1], Yi=geom_in[2], Zi=geom_in[3],
-                  Xo=geom_out[1], Yo=geom_out[2], Zo=geom_out[3], ksize=max(kernel), stride=max(strides), pad=max(pads),
-                  relu=int(relu), tile_hint=TILE_HINT)
-    (d.kx, d.ky, d.kz), (d.px, d.py, d.pz), (d.sx, d.sy, d.sz) = kernel, pads, strides
-    if h2_alpha is not None:
-        d.in_stride, d.mfma_dtype, d.alpha, d.alpha_dev, tag = in_C, 3, float(h2_alpha), alpha_dev, "k_gemm_h2 " + tag
-    launch_conv(d, x2d.device, tag, 2.0 * M * in_C * Cout * taps)
-
-
-class AnisoConvRowsFn(torch.autograd.Function):
-    """y = relu(scale * conv(x, W) + shift) on channels-last rows for a layer with per-axis ``kernel`` / ``strides`` / ``pads``
-    (as ``core.PackedConv`` describes them); weight [Cout,Cin,kx,ky,kz].  Differentiable in x, W and the conv bias."""
-
-    @staticmethod
-    def forward(ctx, x2d, weight, bias, scale, shift, geom, kernel, strides, pads, relu):
-        B, Xi, Yi, Zi = geom
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        taps = kernel[0] * kernel[1] * kernel[2]
-        assert tuple(weight.shape[2:]) == tuple(kernel), "weight %s is not [Cout,Cin,%d,%d,%d]" % ((tuple(weight.shape),) + tuple(kernel))
-        assert x2d.shape == (B * Xi * Yi * Zi, Cin) and x2d.is_contiguous() and Cin % 4 == 0
-        geom_out = (B,) + out_dims3((Xi, Yi, Zi), kernel, strides, pads)
-        out = torch.empty(geom_out[0] * geom_out[1] * geom_out[2] * geom_out[3], Cout, device=x2d.device, dtype=_F32)
-        eff_shift = shift
-        if bias is not None:    # y = scale * (conv + b) + shift
-            eff_shift = (bias.detach() * scale if scale is not None else bias.detach()) + (shift if shift is not None else 0)
-            eff_shift = eff_shift.float().contiguous()
-        w3 = weight.detach().float().contiguous().view(Cout, Cin, taps)
-        if _h2_direct(Cin, 2.0 * out.shape[0] * Cin * Cout * taps):
-            _conv_launch3(_rows_h2(x2d, Cin), Cin, pack_weights_h2_dev(w3, Cout, Cin, taps, 0), out, Cout, taps, geom, geom_out, kernel,
-                          strides, pads, scale, eff_shift, relu, h2_alpha=1.0)
-        else:
-            _conv_launch3(x2d, Cin, pack_weights_dev(w3, Cout, Cin, taps, 0), out, Cout, taps, geom, geom_out, kernel, strides, pads,
-                          scale, eff_shift, relu)
-        ctx.save_for_backward(x2d, weight, out, scale if scale is not None else torch.empty(0, device=x2d.device))
-        ctx.cfg = (geom, geom_out, kernel, strides, pads, relu, bias is not None, scale is not None)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        from . import core
-        x2d, weight, out, scale = ctx.saved_tensors
-        geom, geom_out, kernel, strides, pads, relu, has_bias, has_scale = ctx.cfg
-        scale = scale if has_scale else None
-        B, Xi, Yi, Zi = geom
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        taps = kernel[0] * kernel[1] * kernel[2]
-        Mo, Mi = out.shape[0], x2d.shape[0]
-        dev = x2d.device
-        dout = dout.float().contiguous()
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        unit = strides == (1, 1, 1)
-        Cp = _pad4(Cout)
-        dacc = torch.zeros(Mo, Cp, device=dev, dtype=_F32) if Cp != Cout else torch.empty(Mo, Cp, device=dev, dtype=_F32)
-        dbias = torch.empty(Cout, device=dev, dtype=_F32) if (has_bias and need_b) else None
-        ws = workspace(dev)
-        # split-f16 stride-1 dgrad: the gradient operand's power-of-two scale is chosen on the device (see TRAIN_H2_DGRAD)
-        gscale = None
-        if core.CONV_ENGINE == "h2" and TRAIN_H2_DGRAD and need_x and unit and Cp == Cout and Cout % 32 == 0 and Cin % 4 == 0:
-            gscale = torch.empty(2, device=dev, dtype=_F32)
-        call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cp,
-             None, Cout, 0, ptr(dbias), 0, ptr(ws), ws.numel(), ptr(_amax_word(dev)) if gscale is not None else None,
-             ptr(gscale), TRAIN_H2_GRAD_TARGET)
-        if dbias is not None and scale is not None:
-            dbias = dbias * scale
-        dx = dw = None
-        w3 = weight.detach().float().contiguous().view(Cout, Cin, taps)
-        if need_x:
-            dx = torch.empty(Mi, Cin, device=dev, dtype=_F32)
-            if unit:
-                # dx = conv(dacc, W') with every tap axis flipped (pack mode 2 reverses the mixed-radix tap index = each axis) and
-                # pad' = k - 1 - pad per axis
-                pd = tuple(k - 1 - p for k, p in zip(kernel, pads))
-                if gscale is not None and _h2_direct(Cout, 2.0 * Mi * Cin * Cout * taps):
-                    _conv_launch3(_rows_h2(dacc, Cout, gscale), Cout, pack_weights_h2_dev(w3, Cout, Cin, taps, 2), dx, Cin, taps,
-                                  geom_out, geom, kernel, strides, pd, None, None, False, tag="conv_dgrad", h2_alpha=1.0,
-                                  alpha_dev=ptr(gscale, offset=1))
-                else:
-                    _conv_launch3(dacc, Cp, pack_weights_dev(w3, Cout, Cin, taps, 2), dx, Cin, taps, geom_out, geom, kernel, strides,
-                                  pd, None, None, False, tag="conv_dgrad")
-            else:
-                dx.zero_()          # voxels no output reads (stride 4, k = 3: every fourth column and row) keep a zero gradient
-                for rows_c, taps_c, table_c in dgrad_classes3(dev, B, Xi, Yi, Zi, kernel, strides, pads):
-                    wp = pack_weights_dev(w3.index_select(2, taps_c), Cout, Cin, taps_c.numel(), 3)
-                    _conv_launch(dacc, Cp, wp, dx, Cin, taps_c.numel(), geom_out, geom, max(kernel), max(strides), max(pads), None, None,
-                                 None, False, table=table_c, tag="conv_dgrad", out_rows=rows_c)
-        if need_w:
-            idx, tb_live = live_taps3(dev, B, Xi, Yi, Zi, kernel, strides, pads)
-            nl = idx.numel()
-            dw_live = torch.empty(Cout, Cin, nl, device=dev, dtype=_F32)
-            with _lib.TIMER.region("k_wgrad", 2.0 * Mo * Cin * Cout * nl):
-                call("coocc_conv_wgrad", ptr(x2d), Mi, Cin, ptr(dacc), Cp, ptr(tb_live), Mo, Cin, Cout, nl, ptr(dw_live), 0, ptr(ws),
-                     ws.numel())
-            if nl < taps:       # taps that only ever read padding on this grid: zero gradient
-                dw = torch.zeros(Cout, Cin, taps, device=dev, dtype=_F32)
-                dw.index_copy_(2, idx, dw_live)
-            else:
-                dw = dw_live
-            dw = dw.view(weight.shape)
-        return dx, dw, dbias, None, None, None, None, None, None, None
-
-
-def _triple_is_cubic(kernel, strides, pads):
-    return len(set(kernel)) == 1 and len(set(strides)) == 1 and len(set(pads)) == 1
-
-
-def conv3_bn_rows(x2d, weight, geom, kernel, strides=(1, 1, 1), pads=None, bn=None, bias=None, relu=True, sync=None):
-    """``conv_bn_rows`` for a layer given by per-axis triples; ``weight`` [Cout,Cin,kx,ky,kz] (any strides: a permuted view of a
-    reference [.,.,kz,ky,kx] parameter keeps its gradient).  Cubic triples take ``conv_bn_rows`` (ConvRowsFn and its Winograd
-    routes).  Every BN follows its own ``training`` flag."""
-    kernel, strides = tuple(int(k) for k in kernel), tuple(int(s) for s in strides)
-    pads = tuple(int(p) for p in pads) if pads is not None else tuple((k - 1) // 2 for k in kernel)
-    if _triple_is_cubic(kernel, strides, pads):
-        return conv_bn_rows(x2d, weight, geom, bn=bn, bias=bias, stride=strides[0], pad=pads[0], relu=relu)
-    B, X, Y, Z = geom
-    go = (B,) + out_dims3((X, Y, Z), kernel, strides, pads)
-    x2d = x2d.contiguous()
-    if bn is not None and bn.training:
-        y = AnisoConvRowsFn.apply(x2d, weight, bias, None, None, tuple(geom), kernel, strides, pads, False)
-        return BatchNormRowsFn.apply(y, bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync)), go
-    scale = shift = None
-    if bn is not None:
-        from .core import fold_bn
-        s, b = fold_bn(bn, None)
-        scale, shift = s.to(x2d.device).contiguous(), b.to(x2d.device).contiguous()
-    return AnisoConvRowsFn.apply(x2d, weight, bias, scale, shift, tuple(geom), kernel, strides, pads, relu), go
-
-
+# Training of lidar_trunk's modules.  The anisotropic layers (3x3x1 kernels, strides (s, s, 1), pads (1, 1, 0)) are ConvRowsFn
+# layers like any other: coocc_conv_fwd through the descriptor's per-axis fields, the same launch with flipped weights for the
+# stride-1 dgrad, row-table launches per residue class for the strided one, coocc_conv_wgrad over the live taps.
 class FpnSumFn(torch.autograd.Function):
     """``lidar_trunk.fpn_sum`` on 2-D tensors: ups[l] [B*(X/s)*(Y/s)*Z, s*s*C] (child-major deblock outputs) -> [B*X*Y*Z, C].  The
     backward re-lays dout into every level's own layout (coocc_fpn_sum_bwd); a stride-1 level's gradient is dout itself."""
@@ -1312,7 +1181,7 @@ def deconv_bn_rows(x2d, up, bn, s, relu=True, sync=None):
         from .core import fold_bn
         sc, sh = fold_bn(bn, None)
         scale, shift = sc.repeat(s * s).to(x2d.device).contiguous(), sh.repeat(s * s).to(x2d.device).contiguous()
-    return ConvRowsFn.apply(x2d.contiguous(), w, b, None, scale, shift, (1, n, 1, 1), 1, 1, 0, relu)
+    return ConvRowsFn.apply(x2d.contiguous(), w, b, None, scale, shift, (1, n, 1, 1), _UNIT, _UNIT, _NOPAD, relu)
 
 
 class ZyxRowsFn(torch.autograd.Function):
@@ -1341,14 +1210,13 @@ def _zyx(w):
 
 def second3d_forward_train(backbone, x2d, geom):
     """SECOND3D (second3d.py:91-114) on rows -> [(rows, geom)] per block; the inference module's own parameters."""
-    kz, ky, kx = backbone.kernel
     outs = []
     for i, blk in enumerate(backbone.blocks):
         s = backbone.layer_strides[i]
         h, g = x2d, geom
         for j in range(0, len(blk), 3):
             st = (s, s, 1) if j == 0 else (1, 1, 1)
-            h, g = conv3_bn_rows(h, _zyx(blk[j].weight), g, (kx, ky, kz), st, bn=blk[j + 1], bias=blk[j].bias, relu=True)
+            h, g = conv_bn_rows(h, _zyx(blk[j].weight), g, bn=blk[j + 1], bias=blk[j].bias, stride=st, pad=blk[j].padding[::-1], relu=True)
         outs.append((h, g))
         if backbone.is_cascade:
             x2d, geom = h, g
@@ -1376,8 +1244,7 @@ def second3dfpn_forward_train(neck, feats):
     else:
         out = fpn_sum_rows(ups, neck.upsample_strides, C, fine)
     if neck.extra_conv is not None:
-        kz, ky, kx = neck.extra_kernel
         for j in range(0, len(neck.extra_blocks), 3):
             c, bn = neck.extra_blocks[j], neck.extra_blocks[j + 1]
-            out, fine = conv3_bn_rows(out, _zyx(c.weight), fine, (kx, ky, kz), bn=bn, bias=c.bias, relu=True)
+            out, fine = conv_bn_rows(out, _zyx(c.weight), fine, bn=bn, bias=c.bias, pad=c.padding[::-1], relu=True)
     return out, fine

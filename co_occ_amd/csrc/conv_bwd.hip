@@ -11,6 +11,7 @@
 #include "colreduce.h"
 #include "conv_k.h"
 #include <stdlib.h>
+#include <string.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -115,42 +116,70 @@ extern "C" int64_t coocc_conv_pack_weights_h2_dev(const float* w, int Cout, int 
 }
 
 // ------------------------------------------------------------------ row tables
+// The row tables of a convolution with per-axis kernel / stride / padding (a cubic layer has equal triples; the LiDAR trunk's
+// 3x3x1 layers have strides (s, s, 1), s up to 4).  Tap t = (dx*ky + dy)*kz + dz, rows in (b, x, y, z) order.
 // fwd table  [taps][Mo]: input row read by output voxel o for tap t (or -1: zero padding)
-// dgrad table[taps][Mi]: output row o with o*stride - pad + t == i (or -1)
-__global__ __launch_bounds__(256) void k_tap_table(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int ksize,
-                                                    int stride, int pad, int dgrad, int32_t* __restrict__ table) {
-  const int M = dgrad ? B * Xi * Yi * Zi : B * Xo * Yo * Zo;
-  const int taps = ksize * ksize * ksize;
+// dgrad table[taps][Mi]: output row o with o*stride - pad + t == i per axis (or -1: no output reads this voxel through this tap)
+struct Tap3K {
+  int B, Xi, Yi, Zi, Xo, Yo, Zo;
+  int kx, ky, kz, sx, sy, sz, px, py, pz;
+  int dgrad;
+  long long M;
+  int32_t* table;
+};
+
+__global__ __launch_bounds__(256) void k_tap_table3(Tap3K p) {
+  const long long taps = (long long)p.kx * p.ky * p.kz;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)M * taps) return;
-  const int t = (int)(i / M), m = (int)(i % M);
-  const int kw = t % ksize, kh = (t / ksize) % ksize, kd = t / (ksize * ksize);
-  int r = -1;
-  if (!dgrad) {
-    const int z = m % Zo, y = (m / Zo) % Yo, x = (m / (Zo * Yo)) % Xo, b = m / (Zo * Yo * Xo);
-    const int ix = x * stride - pad + kd, iy = y * stride - pad + kh, iz = z * stride - pad + kw;
-    if ((unsigned)ix < (unsigned)Xi && (unsigned)iy < (unsigned)Yi && (unsigned)iz < (unsigned)Zi)
-      r = ((b * Xi + ix) * Yi + iy) * Zi + iz;
+  if (i >= p.M * taps) return;
+  const int t = (int)(i / p.M);
+  const long long m = i % p.M;
+  const int dz = t % p.kz, dy = (t / p.kz) % p.ky, dx = t / (p.kz * p.ky);
+  long long r = -1;
+  if (!p.dgrad) {
+    const int z = (int)(m % p.Zo), y = (int)((m / p.Zo) % p.Yo), x = (int)((m / ((long long)p.Zo * p.Yo)) % p.Xo);
+    const long long b = m / ((long long)p.Zo * p.Yo * p.Xo);
+    const int ix = x * p.sx - p.px + dx, iy = y * p.sy - p.py + dy, iz = z * p.sz - p.pz + dz;
+    if ((unsigned)ix < (unsigned)p.Xi && (unsigned)iy < (unsigned)p.Yi && (unsigned)iz < (unsigned)p.Zi)
+      r = ((b * p.Xi + ix) * p.Yi + iy) * p.Zi + iz;
   } else {
-    const int z = m % Zi, y = (m / Zi) % Yi, x = (m / (Zi * Yi)) % Xi, b = m / (Zi * Yi * Xi);
-    const int ox = x + pad - kd, oy = y + pad - kh, oz = z + pad - kw;
-    if (ox >= 0 && oy >= 0 && oz >= 0 && ox % stride == 0 && oy % stride == 0 && oz % stride == 0 && ox / stride < Xo &&
-        oy / stride < Yo && oz / stride < Zo)
-      r = ((b * Xo + ox / stride) * Yo + oy / stride) * Zo + oz / stride;
+    const int z = (int)(m % p.Zi), y = (int)((m / p.Zi) % p.Yi), x = (int)((m / ((long long)p.Zi * p.Yi)) % p.Xi);
+    const long long b = m / ((long long)p.Zi * p.Yi * p.Xi);
+    const int ox = x + p.px - dx, oy = y + p.py - dy, oz = z + p.pz - dz;
+    if (ox >= 0 && oy >= 0 && oz >= 0 && ox % p.sx == 0 && oy % p.sy == 0 && oz % p.sz == 0 && ox / p.sx < p.Xo && oy / p.sy < p.Yo &&
+        oz / p.sz < p.Zo)
+      r = ((b * p.Xo + ox / p.sx) * p.Yo + oy / p.sy) * p.Zo + oz / p.sz;
   }
-  table[i] = r;
+  p.table[i] = (int32_t)r;
 }
 
+extern "C" int coocc_conv_tap_table3(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int kx, int ky, int kz, int sx, int sy, int sz,
+                                     int px, int py, int pz, int dgrad, int32_t* table, void* stream) {
+  COOCC_CHECK_ARG(table && B > 0 && Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "conv_tap_table3: null table or empty grid");
+  COOCC_CHECK_ARG(kx > 0 && ky > 0 && kz > 0 && sx > 0 && sy > 0 && sz > 0 && px >= 0 && py >= 0 && pz >= 0 && kx <= 64 && ky <= 64 && kz <= 64,
+                  "conv_tap_table3: kernel extents 1..64, strides >= 1, paddings >= 0 per axis");
+  COOCC_CHECK_ARG(Xi + 2 * px >= kx && Yi + 2 * py >= ky && Zi + 2 * pz >= kz && Xo == (Xi + 2 * px - kx) / sx + 1 &&
+                      Yo == (Yi + 2 * py - ky) / sy + 1 && Zo == (Zi + 2 * pz - kz) / sz + 1,
+                  "conv_tap_table3: output extents (%d,%d,%d) are not (n + 2p - k) / s + 1 of input (%d,%d,%d)", Xo, Yo, Zo, Xi, Yi, Zi);
+  Tap3K p;
+  memset(&p, 0, sizeof(p));
+  p.B = B; p.Xi = Xi; p.Yi = Yi; p.Zi = Zi; p.Xo = Xo; p.Yo = Yo; p.Zo = Zo;
+  p.kx = kx; p.ky = ky; p.kz = kz; p.sx = sx; p.sy = sy; p.sz = sz; p.px = px; p.py = py; p.pz = pz;
+  p.dgrad = dgrad ? 1 : 0;
+  const long long Mi = (long long)B * Xi * Yi * Zi, Mo = (long long)B * Xo * Yo * Zo;
+  p.M = dgrad ? Mi : Mo;
+  const long long taps = (long long)kx * ky * kz;
+  COOCC_CHECK_ARG(p.M * taps < (1ll << 31) && Mi < (1ll << 31) && Mo < (1ll << 31), "conv_tap_table3: too large (32-bit rows)");
+  p.table = table;
+  hipLaunchKernelGGL(k_tap_table3, dim3(cdiv(p.M * taps, 256)), dim3(256), 0, as_stream(stream), p);
+  COOCC_LAUNCH_CHECK("k_tap_table3");
+  return COOCC_OK;
+}
+
+// the cubic form: the per-axis entry with equal triples (and with its checks, the extent check included)
 extern "C" int coocc_conv_tap_table(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int ksize, int stride, int pad,
                                     int dgrad, int32_t* table, void* stream) {
-  COOCC_CHECK_ARG(table && B > 0 && Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0 && ksize > 0 && stride > 0 && pad >= 0,
-                  "conv_tap_table: bad args");
-  const long long M = dgrad ? (long long)B * Xi * Yi * Zi : (long long)B * Xo * Yo * Zo;
-  COOCC_CHECK_ARG(M * ksize * ksize * ksize < (1ll << 31) && (long long)B * Xi * Yi * Zi < (1ll << 31), "conv_tap_table: too large");
-  hipLaunchKernelGGL(k_tap_table, dim3(cdiv(M * ksize * ksize * ksize, 256)), dim3(256), 0, as_stream(stream), B, Xi, Yi, Zi, Xo,
-                     Yo, Zo, ksize, stride, pad, dgrad, table);
-  COOCC_LAUNCH_CHECK("k_tap_table");
-  return COOCC_OK;
+  return coocc_conv_tap_table3(B, Xi, Yi, Zi, Xo, Yo, Zo, ksize, ksize, ksize, stride, stride, stride, pad, pad, pad, dgrad, table, stream);
 }
 
 // ------------------------------------------------------------------ epilogue backward

@@ -1,8 +1,5 @@
-// Training of the LiDAR-only trunk (SECOND3D + SECOND3DFPN, co_occ_amd/lidar_trunk.py run_trunk_train): what the table-driven
-// backward of the conv family (csrc/conv_bwd.hip) did not have yet.
-//  * k_tap_table3: the row tables of a convolution with per-axis kernel / stride / padding -- the backbone's 3x3x1 layers with
-//    strides (s, s, 1), s up to 4.  Same conventions as k_tap_table (tap t = (dx*ky + dy)*kz + dz, rows in (b, x, y, z) order, -1
-//    for padding / "no output reads this voxel through this tap"); for cubic arguments the same table.
+// Training of the LiDAR-only trunk (SECOND3D + SECOND3DFPN, co_occ_amd/lidar_trunk.py run_trunk_train): the one kernel the
+// table-driven backward of the conv family (csrc/conv_bwd.hip, whose row tables take per-axis kernel / stride / padding) lacks.
 //  * k_fpn_sum_bwd: backward of k_fpn_sum (csrc/second_fpn.hip).  d sum / d level = 1, so every level's gradient is dout itself,
 //    re-laid into that deblock's child-major rows [B*(X/s)*(Y/s)*Z][s*s][C]: a pure gather-free scatter of whole rows, every fine
 //    voxel owning exactly one child slot per level.  dout is read once for all levels.  HBM-bound: (1 + levels written) * rows * C * 4 bytes.
@@ -11,62 +8,6 @@
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Tap3K {
-  int B, Xi, Yi, Zi, Xo, Yo, Zo;
-  int kx, ky, kz, sx, sy, sz, px, py, pz;
-  int dgrad;
-  long long M;
-  int32_t* table;
-};
-
-__global__ __launch_bounds__(256) void k_tap_table3(Tap3K p) {
-  const long long taps = (long long)p.kx * p.ky * p.kz;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.M * taps) return;
-  const int t = (int)(i / p.M);
-  const long long m = i % p.M;
-  const int dz = t % p.kz, dy = (t / p.kz) % p.ky, dx = t / (p.kz * p.ky);
-  long long r = -1;
-  if (!p.dgrad) {
-    const int z = (int)(m % p.Zo), y = (int)((m / p.Zo) % p.Yo), x = (int)((m / ((long long)p.Zo * p.Yo)) % p.Xo);
-    const long long b = m / ((long long)p.Zo * p.Yo * p.Xo);
-    const int ix = x * p.sx - p.px + dx, iy = y * p.sy - p.py + dy, iz = z * p.sz - p.pz + dz;
-    if ((unsigned)ix < (unsigned)p.Xi && (unsigned)iy < (unsigned)p.Yi && (unsigned)iz < (unsigned)p.Zi)
-      r = ((b * p.Xi + ix) * p.Yi + iy) * p.Zi + iz;
-  } else {
-    const int z = (int)(m % p.Zi), y = (int)((m / p.Zi) % p.Yi), x = (int)((m / ((long long)p.Zi * p.Yi)) % p.Xi);
-    const long long b = m / ((long long)p.Zi * p.Yi * p.Xi);
-    const int ox = x + p.px - dx, oy = y + p.py - dy, oz = z + p.pz - dz;
-    if (ox >= 0 && oy >= 0 && oz >= 0 && ox % p.sx == 0 && oy % p.sy == 0 && oz % p.sz == 0 && ox / p.sx < p.Xo && oy / p.sy < p.Yo &&
-        oz / p.sz < p.Zo)
-      r = ((b * p.Xo + ox / p.sx) * p.Yo + oy / p.sy) * p.Zo + oz / p.sz;
-  }
-  p.table[i] = (int32_t)r;
-}
-
-extern "C" int coocc_conv_tap_table3(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int kx, int ky, int kz, int sx, int sy, int sz,
-                                     int px, int py, int pz, int dgrad, int32_t* table, void* stream) {
-  COOCC_CHECK_ARG(table && B > 0 && Xi > 0 && Yi > 0 && Zi > 0 && Xo > 0 && Yo > 0 && Zo > 0, "conv_tap_table3: null table or empty grid");
-  COOCC_CHECK_ARG(kx > 0 && ky > 0 && kz > 0 && sx > 0 && sy > 0 && sz > 0 && px >= 0 && py >= 0 && pz >= 0 && kx <= 64 && ky <= 64 && kz <= 64,
-                  "conv_tap_table3: kernel extents 1..64, strides >= 1, paddings >= 0 per axis");
-  COOCC_CHECK_ARG(Xi + 2 * px >= kx && Yi + 2 * py >= ky && Zi + 2 * pz >= kz && Xo == (Xi + 2 * px - kx) / sx + 1 &&
-                      Yo == (Yi + 2 * py - ky) / sy + 1 && Zo == (Zi + 2 * pz - kz) / sz + 1,
-                  "conv_tap_table3: output extents (%d,%d,%d) are not (n + 2p - k) / s + 1 of input (%d,%d,%d)", Xo, Yo, Zo, Xi, Yi, Zi);
-  Tap3K p;
-  memset(&p, 0, sizeof(p));
-  p.B = B; p.Xi = Xi; p.Yi = Yi; p.Zi = Zi; p.Xo = Xo; p.Yo = Yo; p.Zo = Zo;
-  p.kx = kx; p.ky = ky; p.kz = kz; p.sx = sx; p.sy = sy; p.sz = sz; p.px = px; p.py = py; p.pz = pz;
-  p.dgrad = dgrad ? 1 : 0;
-  const long long Mi = (long long)B * Xi * Yi * Zi, Mo = (long long)B * Xo * Yo * Zo;
-  p.M = dgrad ? Mi : Mo;
-  const long long taps = (long long)kx * ky * kz;
-  COOCC_CHECK_ARG(p.M * taps < (1ll << 31) && Mi < (1ll << 31) && Mo < (1ll << 31), "conv_tap_table3: too large (32-bit rows)");
-  p.table = table;
-  hipLaunchKernelGGL(k_tap_table3, dim3(cdiv(p.M * taps, 256)), dim3(256), 0, as_stream(stream), p);
-  COOCC_LAUNCH_CHECK("k_tap_table3");
-  return COOCC_OK;
-}
 
 struct FpnSumBwdK {
   const float* dout;     // [B*X*Y*Z][dout_stride], C channels

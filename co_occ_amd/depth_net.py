@@ -14,11 +14,12 @@ the reference's names; ``DepthNet.forward`` is the one forward.  No CPU or eager
 
 Training is opt-in (``DepthNet.train_enabled``, default False: ``train()`` then raises).  With it on, the ``train()`` forward is
 differentiable in every parameter and in x: batch-statistics BN on rows (``autograd.BatchNormRowsFn``; running statistics updated
-as torch does), the 3x3 layers through ``autograd.conv3_bn_rows``, the 1x1 layers / MLPs through ``autograd.linear_rows``, the
-dilated branches through ``lidar_hd.SparseConvV1Fn`` over the live-tap rows of the neighbour table, and the Functions below over
-the training kernels of csrc/depthnet.hip: the deformable convolution (``DcnRowsFn``: column matrices recomputed per chunk in the
-backward, dx by fp32 atomics -- the one place whose bits may differ from run to run), the SE gates, the camera means / camera
-vector of the pooled branch (added un-normalised before ``bn1``), dropout with a device-drawn mask.
+as torch does), the 3x3 layers through ``autograd.conv_bn_rows`` as 3x3x1 kernels (``autograd.ConvRowsFn``, the Function of every
+dense convolution), the 1x1 layers / MLPs through ``autograd.linear_rows``, the dilated branches through
+``lidar_hd.SparseConvV1Fn`` over the live-tap rows of the neighbour table, and the Functions below over the training kernels of
+csrc/depthnet.hip: the deformable convolution (``DcnRowsFn``: column matrices recomputed per chunk in the backward, dx by fp32
+atomics -- the one place whose bits may differ from run to run), the SE gates, the camera means / camera vector of the pooled
+branch (added un-normalised before ``bn1``), dropout with a device-drawn mask.
 """
 import math
 
@@ -503,12 +504,12 @@ def bn_rows(y, bn, relu=False, res=None):
 
 
 def conv3x3_train(x2d, geom, weight, bn=None, bias=None, relu=True, res=None):
-    """Conv2d 3x3 padding 1 (-> batch-statistics BN (+ res)) (-> ReLU) on rows through ``autograd.conv3_bn_rows`` with kernel (3, 3, 1)."""
+    """Conv2d 3x3 padding 1 (-> batch-statistics BN (+ res)) (-> ReLU) on rows through ``autograd.conv_bn_rows`` with kernel (3, 3, 1)."""
     ag = _ag()
     w5 = weight.unsqueeze(-1)
     if bn is None or res is None:
-        return ag.conv3_bn_rows(x2d, w5, geom, (3, 3, 1), bn=bn, bias=bias, relu=relu)[0]
-    y = ag.conv3_bn_rows(x2d, w5, geom, (3, 3, 1), bn=None, bias=bias, relu=False)[0]
+        return ag.conv_bn_rows(x2d, w5, geom, bn=bn, bias=bias, relu=relu)[0]
+    y = ag.conv_bn_rows(x2d, w5, geom, bn=None, bias=bias, relu=False)[0]
     return bn_rows(y, bn, relu=relu, res=res)
 
 

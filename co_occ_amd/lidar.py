@@ -176,20 +176,13 @@ def _inverse_table(table, n_in):
     return inv
 
 
-def _table_launch(x2d, in_C, w_packed, out2d, Cout, table, bias=None, tag="sparse"):
-    from .autograd import _conv_launch
-    n_in = x2d.shape[0]
-    _conv_launch(x2d, in_C, w_packed, out2d, Cout, table.shape[0], (1, n_in, 1, 1), (1, out2d.shape[0], 1, 1), 1, 1, 0, None, bias,
-                 None, False, table=table, tag=tag)
-
-
 class SparseConvFn(torch.autograd.Function):
     """y = sparse_conv(x; W, table) (+ bias): SubMConv3d / SparseConv3d of spconv 2.x on rows, differentiable in x, W, b.
     ``weight``: [Cout, k, k, k, Cin] (the reference's state_dict layout); x: [n_in, pad4(Cin)]."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, table, table_bwd):
-        from .autograd import pack_weights_dev
+        from .autograd import _table_launch, pack_weights_dev
         Cout, Cin = weight.shape[0], weight.shape[-1]
         taps, Mo = table.shape
         Cp = x.shape[1]
@@ -200,14 +193,14 @@ class SparseConvFn(torch.autograd.Function):
         out = torch.empty(Mo, Cout, device=x.device, dtype=_F32)
         if Mo:
             _table_launch(x, Cp, pack_weights_dev(w3, Cout, Cp, taps, 1), out, Cout, table,
-                          bias=bias.detach().float().contiguous() if bias is not None else None, tag="sparse_fwd")
+                          shift=bias.detach().float().contiguous() if bias is not None else None, tag="sparse_fwd")
         ctx.save_for_backward(x, w3, table, table_bwd)
         ctx.cfg = (Cin, bias is not None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        from .autograd import pack_weights_dev, _pad4 as pad4
+        from .autograd import _table_launch, pack_weights_dev, _pad4 as pad4
         x, w3, table, table_bwd = ctx.saved_tensors
         Cin, has_bias = ctx.cfg
         Cout, taps, Cp = w3.shape

@@ -301,14 +301,13 @@ class SparseConvV1Fn(torch.autograd.Function):
         out = torch.empty(Mo, Cout, device=x.device, dtype=_F32)
         h2 = _train_h2()
         if Mo:
-            geo = ((1, n_in, 1, 1), (1, Mo, 1, 1), 1, 1, 0, scale, shift, res, relu)
+            epi = dict(scale=scale, shift=shift, res2d=res, relu=relu, tag="sparse_hd_fwd")
             if h2 and Cp % 32 == 0:
                 xh = x_h2 if x_h2 is not None else ag._rows_h2(x, Cp)
-                ag._conv_launch(xh, Cp, ag.pack_weights_h2_dev(w3, Cout, Cp, taps, 0), out, Cout, taps, *geo, table=table,
-                                tag="sparse_hd_fwd", h2_alpha=1.0)
+                ag._table_launch(xh, Cp, ag.pack_weights_h2_dev(w3, Cout, Cp, taps, 0), out, Cout, table, h2_alpha=1.0, **epi)
             else:
-                ag._conv_launch(x, Cp, ag.pack_weights_dev(w3, Cout, Cp, taps, 0), out, Cout, taps, *geo, table=table, tag="sparse_hd_fwd")
-        ctx.save_for_backward(x, w3, table, out if relu else None, scale, *(bwd if torch.is_tensor(bwd) else [t for c in bwd for t in c]))
+                ag._table_launch(x, Cp, ag.pack_weights_dev(w3, Cout, Cp, taps, 0), out, Cout, table, **epi)
+        ctx.save_for_backward(x, w3, table, out if relu else None, scale, *([bwd] if torch.is_tensor(bwd) else [t for c in bwd for t in c]))
         ctx.cfg = (Cin, tuple(weight.shape), torch.is_tensor(bwd), h2, bool(relu), res is not None)
         return out
 
@@ -344,16 +343,14 @@ class SparseConvV1Fn(torch.autograd.Function):
                 src = ag._rows_h2(dacc, Cout, gscale) if h2d else dacc
                 kw = dict(h2_alpha=1.0, alpha_dev=ptr(gscale, offset=1)) if h2d else {}
                 pack = ag.pack_weights_h2_dev if h2d else ag.pack_weights_dev
-                gi, go = (1, Mo, 1, 1), (1, n_in, 1, 1)
                 if full:
-                    ag._conv_launch(src, Cout, pack(w3, Cout, Cp, taps, 3), dx, Cp, taps, gi, go, 1, 1, 0, None, None, None, False,
-                                    table=books[0], tag="sparse_hd_dgrad", **kw)
+                    ag._table_launch(src, Cout, pack(w3, Cout, Cp, taps, 3), dx, Cp, books[0], tag="sparse_hd_dgrad", **kw)
                 else:
                     for j in range(0, len(books), 3):
                         rows_c, taps_c, table_c = books[j:j + 3]
                         wsub = w3.index_select(2, taps_c).contiguous()
-                        ag._conv_launch(src, Cout, pack(wsub, Cout, Cp, taps_c.numel(), 3), dx, Cp, taps_c.numel(), gi, go, 1, 1, 0, None,
-                                        None, None, False, table=table_c, tag="sparse_hd_dgrad", out_rows=rows_c, **kw)
+                        ag._table_launch(src, Cout, pack(wsub, Cout, Cp, taps_c.numel(), 3), dx, Cp, table_c, tag="sparse_hd_dgrad",
+                                         out_rows=rows_c, **kw)
         if need_w:
             dw3 = torch.zeros(Cout, Cp, taps, device=dev, dtype=_F32)
             if Mo:

@@ -397,8 +397,9 @@ int coocc_wino_wgrad_h2(const void* V_kh2, const void* dM_kh2, int64_t group_row
  * 3: data-gradient pack, taps unflipped (use with a dgrad row table).  packed == NULL returns the float count. */
 int64_t coocc_conv_pack_weights_dev(const float* w, int Cout, int Cin, int taps, int mode, float* packed,
                                     void* stream);
-/* Row tables of a conv geometry: dgrad == 0: [taps][Mo] input row read by output o for tap t (-1 = padding);
- * dgrad != 0: [taps][Mi] output row o with o*stride - pad + t == i (-1 = none). */
+/* Row tables of a cubic conv geometry: dgrad == 0: [taps][Mo] input row read by output o for tap t (-1 = padding);
+ * dgrad != 0: [taps][Mi] output row o with o*stride - pad + t == i (-1 = none).  This is coocc_conv_tap_table3 (below) called
+ * with equal triples, so its checks apply: the extents must be (n + 2*pad - ksize) / stride + 1 of the input's. */
 int coocc_conv_tap_table(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int ksize, int stride, int pad,
                          int dgrad, int32_t* table, void* stream);
 /* dpre = dout * (out > 0 if relu);  dres (+)= dpre;  dacc = dpre * scale;  dbias (+)= column sums of dpre
@@ -879,7 +880,8 @@ int coocc_zyx_to_rows(const float* src, float* dst, int B, int C, int Z, int Y, 
  * 3x3x1 convolutions with strides (s,s,1) (second3d.py:52-77).  Same conventions: table[taps][M] int32, tap t = (dx*ky + dy)*kz + dz,
  * rows in (b,x,y,z) order; dgrad == 0: M = B*Xo*Yo*Zo, the input row output o reads through tap t (-1 = padding); dgrad != 0:
  * M = B*Xi*Yi*Zi, the output row o with o*s - p + d == i per axis (-1 = none: with s > k - 1 some input voxels are read by no
- * output at all).  For cubic arguments the table of coocc_conv_tap_table.  The extents are checked against (n + 2p - k)/s + 1. */
+ * output at all).  The one tap-table kernel (csrc/conv_bwd.hip): coocc_conv_tap_table is this entry with equal triples.  The
+ * extents are checked against (n + 2p - k)/s + 1. */
 int coocc_conv_tap_table3(int B, int Xi, int Yi, int Zi, int Xo, int Yo, int Zo, int kx, int ky, int kz, int sx, int sy, int sz,
                           int px, int py, int pz, int dgrad, int32_t* table, void* stream);
 /* Backward of coocc_fpn_sum: every level's gradient is dout [B*X*Y*Z][dout_stride] (C channels) re-laid into that deblock's own

@@ -1,5 +1,5 @@
-"""Training of the LiDAR-only trunk on the GPU (``lidar_trunk.run_trunk_train``, co_occ_amd/autograd.py, csrc/trunk_train.hip): the
-per-axis row tables against a numpy brute-force book, the backward of the sum kernel bit for bit, one anisotropic layer and one
+"""Training of the LiDAR-only trunk on the GPU (``lidar_trunk.run_trunk_train``, co_occ_amd/autograd.py, csrc/conv_bwd.hip's row
+tables, csrc/trunk_train.hip): the per-axis row tables against a numpy brute-force book, the backward of the sum kernel bit for bit, one anisotropic layer and one
 deblock against float64 torch autograd, a small whole trunk against the plain-torch restatement (tests/ref_second3d.py) under
 ``train()``, the detector's ``train_lidar_trunk`` option end to end, and the co-runner guard of the new re-layout kernel."""
 import copy
@@ -46,13 +46,18 @@ def book(B, dims, kernel, strides, pads):
 
 
 def _table3(dev, B, dims, kernel, strides, pads, dgrad):
-    return ag.tap_table3(dev, B, *dims, tuple(kernel), tuple(strides), tuple(pads), dgrad).cpu().numpy()
+    return ag.tap_table(dev, B, *dims, tuple(kernel), tuple(strides), tuple(pads), dgrad).cpu().numpy()
 
 
-@pytest.mark.parametrize("s", [1, 2, 4])
-@pytest.mark.parametrize("grid", [(9, 7, 2), (8, 8, 1), (6, 5, 3)])
-def test_tap_table3_equals_the_brute_force_book(dev, grid, s):
-    kernel, strides, pads, B = (3, 3, 1), (s, s, 1), (1, 1, 0), 2
+# 3x3x1 kernels at strides (s, s, 1) on every grid, and the cubic geometries of the decoder trunk on (6, 5, 3)
+_GRIDS = [(9, 7, 2), (8, 8, 1), (6, 5, 3)]
+_BOOKS = [pytest.param(g, (3, 3, 1), (s, s, 1), (1, 1, 0), id="grid%d-%d" % (i, s)) for s in (1, 2, 4) for i, g in enumerate(_GRIDS)] + \
+         [pytest.param((6, 5, 3), (k,) * 3, (s,) * 3, (k // 2,) * 3, id="cubic-k%d-s%d" % (k, s)) for k, s in ((3, 1), (3, 2), (1, 2))]
+
+
+@pytest.mark.parametrize("grid, kernel, strides, pads", _BOOKS)
+def test_tap_table3_equals_the_brute_force_book(dev, grid, kernel, strides, pads):
+    B, s = 2, strides[0]
     fwd, dg, _ = book(B, grid, kernel, strides, pads)
     assert np.array_equal(_table3(dev, B, grid, kernel, strides, pads, False), fwd)
     got = _table3(dev, B, grid, kernel, strides, pads, True)
@@ -68,14 +73,22 @@ def test_tap_table3_equals_the_brute_force_book(dev, grid, s):
 @pytest.mark.parametrize("stride", [1, 2])
 @pytest.mark.parametrize("k", [3, 1])
 def test_tap_table3_with_cubic_arguments_is_the_scalar_table(dev, k, stride):
+    """The two C entries on the same grid, bit for bit: ``coocc_conv_tap_table`` is ``coocc_conv_tap_table3`` with equal triples,
+    its extent check included."""
     B, (X, Y, Z), pad = 2, (6, 5, 3), k // 2
+    Xo, Yo, Zo = (core.out_dim(n, k, stride, pad) for n in (X, Y, Z))
     for dgrad in (False, True):
-        want = ag.tap_table(dev, B, X, Y, Z, k, stride, pad, dgrad)
-        got = ag.tap_table3(dev, B, X, Y, Z, (k,) * 3, (stride,) * 3, (pad,) * 3, dgrad)
-        assert got.shape == want.shape and torch.equal(got, want)
+        M = B * X * Y * Z if dgrad else B * Xo * Yo * Zo
+        want = torch.full((k ** 3, M), -7, dtype=torch.int32, device=dev)
+        got = torch.full((k ** 3, M), -9, dtype=torch.int32, device=dev)
+        call("coocc_conv_tap_table", B, X, Y, Z, Xo, Yo, Zo, k, stride, pad, int(dgrad), ptr(want))
+        call("coocc_conv_tap_table3", B, X, Y, Z, Xo, Yo, Zo, k, k, k, stride, stride, stride, pad, pad, pad, int(dgrad), ptr(got))
+        assert torch.equal(got, want) and int(got.min()) >= -1 and int(got.max()) >= 0
+    t = torch.empty(27, 100, dtype=torch.int32, device=dev)
     with pytest.raises(pkg._lib.CooccArgError, match="extents"):
-        t = torch.empty(9, 100, dtype=torch.int32, device=dev)
         call("coocc_conv_tap_table3", 1, 9, 7, 2, 2, 2, 2, 3, 3, 1, 4, 4, 1, 1, 1, 0, 0, ptr(t))
+    with pytest.raises(pkg._lib.CooccArgError, match="extents"):           # (6 + 2 - 3) // 2 + 1 = 3 outputs along x, not 2
+        call("coocc_conv_tap_table", 1, 6, 5, 3, 2, 3, 2, 3, 2, 1, 0, ptr(t))
 
 
 # ------------------------------------------------------------------ b. backward of the sum kernel
@@ -123,13 +136,16 @@ def _gather(rows, idx):
 
 @pytest.mark.parametrize("Cin, Cout", [(32, 64), (8, 12)])
 @pytest.mark.parametrize("s", [1, 2, 4])
-@pytest.mark.parametrize("grid", [(9, 7, 2), (8, 8, 1)])
-def test_anisotropic_layer_forward_dgrad_wgrad_against_float64(dev, monkeypatch, grid, s, Cin, Cout):
+@pytest.mark.parametrize("grid, res", [pytest.param((9, 7, 2), False, id="grid0"), pytest.param((8, 8, 1), False, id="grid1"),
+                                       pytest.param((8, 8, 1), True, id="grid1-res")])
+def test_anisotropic_layer_forward_dgrad_wgrad_against_float64(dev, monkeypatch, grid, res, s, Cin, Cout):
     """3x3x1 kernel, strides (s, s, 1), pads (1, 1, 0), conv + ReLU: forward, dx and dW against float64 autograd of F.conv3d with
     the ReLU mask of the kernel's own forward (as ``util.train_judge``), judged by ``util.assert_precise``.  Anchors: the fp32
     evaluation in the MFMA's accumulation order (chain = 2) and, on the split-f16 routes, the split emulation with the gradient
     operand scaled as the device scales it.  (32, 64) takes the split-f16 GEMMs (with the flop floor lifted, as the precision tests
-    do), (8, 12) the fp32-MFMA ones; the strided dgrad and the weight gradient are fp32-MFMA launches on either."""
+    do), (8, 12) the fp32-MFMA ones; the strided dgrad and the weight gradient are fp32-MFMA launches on either.  ``res``: a random
+    [Mo, Cout] residual added before the ReLU -- the float64 reference adds it too, and its gradient is dy under the ReLU mask,
+    bit for bit (the epilogue's backward copies it)."""
     monkeypatch.setattr(core, "H2_DIRECT_MIN_FLOPS", 0.0)
     h2 = Cin % 32 == 0
     kernel, strides, pads = (3, 3, 1), (s, s, 1), (1, 1, 0)
@@ -139,10 +155,12 @@ def test_anisotropic_layer_forward_dgrad_wgrad_against_float64(dev, monkeypatch,
     w = torch.randn(Cout, Cin, 3, 3, 1, generator=gen) * (2.0 / (9 * Cin)) ** 0.5
     fwd, dg, (Xo, Yo, Zo) = book(1, grid, kernel, strides, pads)
     up = torch.randn(1, Cout, Xo, Yo, Zo, generator=gen)
+    r2 = torch.randn(Xo * Yo * Zo, Cout, generator=gen) if res else None
     xd = util.ncdhw_rows(x).contiguous().to(dev).requires_grad_()
     wd = w.to(dev).requires_grad_()
+    rd = r2.to(dev).requires_grad_() if res else None
     with util.kernels() as names:
-        yd, go = ag.conv3_bn_rows(xd, wd, (1, X, Y, Z), kernel, strides, relu=True)
+        yd, go = ag.conv_bn_rows(xd, wd, (1, X, Y, Z), stride=strides, relu=True, res2d=rd)
         yd.backward(util.ncdhw_rows(up).contiguous().to(dev))
     core.check_h2_overflow()
     assert go == (1, Xo, Yo, Zo)
@@ -156,11 +174,14 @@ def test_anisotropic_layer_forward_dgrad_wgrad_against_float64(dev, monkeypatch,
     if s == 4:                  # classes (x mod 4, y mod 4) with a 2 are reached through no tap: 3 x 3 classes at most
         assert names["conv_dgrad"] <= 9, names
     # forward
-    r64, r32, rs = util.gemm_refs(conv_taps_axes(x, w, strides), chain=2, split=h2, relu=True)
+    r64, r32, rs = util.gemm_refs(conv_taps_axes(x, w, strides), chain=2, split=h2, res=r2, relu=True)
     yk = yd.detach().cpu()
-    util.assert_precise(yk, r64, r32, rs, what="aniso fwd s%d %s %d->%d" % (s, grid, Cin, Cout))
+    util.assert_precise(yk, r64, r32, rs, what="aniso fwd s%d %s %d->%d res=%s" % (s, grid, Cin, Cout, res))
     # backward, ReLU mask of the kernel's own forward
     dy_rows = util.ncdhw_rows(up) * (yk > 0)
+    if res:                     # the masked entries are +0 (a select; the product dy * 0 would carry dy's sign into the zero)
+        assert bits_equal(rd.grad.cpu(), torch.where(yk > 0, util.ncdhw_rows(up), torch.zeros(()))) and torch.equal(rd.grad.cpu(), dy_rows), \
+            "the residual's gradient is dy under the ReLU mask, bit for bit"
     dy = dy_rows.view(1, Xo, Yo, Zo, Cout).permute(0, 4, 1, 2, 3)
     xa, wa = x.double().requires_grad_(), w.double().requires_grad_()
     F.conv3d(xa, wa, stride=strides, padding=pads).backward(dy.double())
