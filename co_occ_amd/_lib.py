@@ -203,6 +203,10 @@ SIGNATURES = {
     "coocc_cam_add": (I, [P, P, I, I, I, P, F, P]),
     "coocc_dropout_rows": (I, [P, P, L, I, F, P, P]),
     "coocc_img_stem": (I, [P, I, I, I, P, P, P, I, I, I, P, I, P, P]),
+    "coocc_maxpool2d_rows": (I, [P, I, I, I, I, I, P, I, P, P]),
+    "coocc_maxpool2d_rows_bwd": (I, [P, I, P, I, I, I, I, I, P, I, P]),
+    "coocc_img_stem_wgrad_ws": (Z, [I, I, I]),
+    "coocc_img_stem_wgrad": (I, [P, I, I, I, P, I, I, P, P, Z, P]),
 }
 
 _lib = None

@@ -1248,3 +1248,125 @@ def second3dfpn_forward_train(neck, feats):
             c, bn = neck.extra_blocks[j], neck.extra_blocks[j + 1]
             out, fine = conv_bn_rows(out, _zyx(c.weight), fine, bn=bn, bias=c.bias, pad=c.padding[::-1], relu=True)
     return out, fine
+
+
+# ----------------------------------------------------------------------------- image encoder (ResNet stem, SECONDFPN deblocks)
+# Training of image_encoder's modules.  Every Bottleneck layer and the neck's convolutions are ConvRowsFn layers on rows
+# [BN*H*W, C] (X = H, Y = W, Z = 1); what the engine lacked is the stem (csrc/img_stem_train.hip).
+class StemConvFn(torch.autograd.Function):
+    """y = relu(scale * conv7x7/2(img, W) + shift) of the fp32 NCHW image [BN,3,H,W] -> rows [BN*Hc*Wc, 64] (k_img_stem without the
+    pool); weight [64,3,7,7]; scale / shift constants (a folded eval-mode BN) or None.  Differentiable in W (coocc_img_stem_wgrad);
+    the image gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, img, weight, scale, shift, relu):
+        if ctx.needs_input_grad[0] or img.requires_grad:
+            raise NotImplementedError("StemConvFn: a gradient with respect to the image is not built")
+        img = img.detach().float().contiguous()
+        BN, _, H, W = img.shape
+        C0 = weight.shape[0]
+        assert tuple(weight.shape[1:]) == (3, 7, 7)
+        dev = img.device
+        w = weight.detach().float().permute(1, 2, 3, 0).reshape(147, C0).contiguous()
+        sc = scale if scale is not None else torch.ones(C0, device=dev, dtype=_F32)
+        sh = shift if shift is not None else torch.zeros(C0, device=dev, dtype=_F32)
+        Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        out = torch.empty(BN * Hc * Wc, C0, device=dev, dtype=_F32)
+        with _lib.TIMER.region("k_img_stem", 2.0 * out.shape[0] * C0 * 147):
+            call("coocc_img_stem", ptr(img), BN, H, W, ptr(w), ptr(sc), ptr(sh), C0, int(relu), 0, ptr(out), C0, None)
+        ctx.save_for_backward(img, out, scale if scale is not None else torch.empty(0, device=dev))
+        ctx.cfg = (scale is not None, bool(relu), tuple(weight.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        img, out, scale = ctx.saved_tensors
+        has_scale, relu, wshape = ctx.cfg
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        BN, _, H, W = img.shape
+        C0 = wshape[0]
+        dev = img.device
+        dacc = dout.float().contiguous()
+        if has_scale or relu:
+            dy, dacc = dacc, torch.empty_like(dacc)
+            ws = workspace(dev)
+            call("coocc_conv_epilogue_bwd_ex", ptr(dy), C0, ptr(out), C0, ptr(scale) if has_scale else None, out.shape[0], C0, int(relu),
+                 ptr(dacc), C0, None, C0, 0, None, 0, ptr(ws), ws.numel(), None, None, TRAIN_H2_GRAD_TARGET)
+        dw = torch.empty(147, C0, device=dev, dtype=_F32)
+        nb = int(_lib.load().coocc_img_stem_wgrad_ws(BN, H, W))
+        part = stream_buffer(dev, "s:stem_wgrad", (nb + 3) // 4)
+        with _lib.TIMER.region("k_img_stem_wgrad", 2.0 * out.shape[0] * C0 * 147):
+            call("coocc_img_stem_wgrad", ptr(img), BN, H, W, ptr(dacc), C0, C0, ptr(dw), ptr(part), part.numel() * 4)
+        return None, dw.view(3, 7, 7, C0).permute(3, 0, 1, 2), None, None, None
+
+
+def stem_conv_bn_rows(img, conv, bn, relu=True, sync=None):
+    """The ResNet stem's Conv2d(3, 64, 7, 2, 3) -> BN -> ReLU on rows with the norm layer's own mode (as ``conv_bn_rows``) ->
+    (rows [BN*Hc*Wc, 64], (BN, Hc, Wc, 1))."""
+    from .core import fold_bn
+    BN, _, H, W = img.shape
+    geom = (BN, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 1)
+    if bn.training:
+        y = StemConvFn.apply(img, conv.weight, None, None, False)
+        return BatchNormRowsFn.apply(y, bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync)), geom
+    s, b = fold_bn(bn, conv.bias)
+    return StemConvFn.apply(img, conv.weight, s.to(img.device).contiguous(), b.to(img.device).contiguous(), relu), geom
+
+
+class MaxPoolRowsFn(torch.autograd.Function):
+    """MaxPool2d(3, 2, 1) on rows [BN*Hc*Wc, C] -> [BN*Hp*Wp, C] (coocc_maxpool2d_rows).  No index tensor is kept: the backward
+    recomputes every window's first maximum from the pre-pool rows, which their producer (the BN / ReLU pass) saves anyway."""
+
+    @staticmethod
+    def forward(ctx, x2d, geom):
+        BN, Hc, Wc = geom
+        x2d = x2d.float().contiguous()
+        C = x2d.shape[1]
+        assert x2d.shape[0] == BN * Hc * Wc and C % 4 == 0
+        Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+        out = torch.empty(BN * Hp * Wp, C, device=x2d.device, dtype=_F32)
+        with _lib.TIMER.region("k_maxpool2d_rows", 9.0 * out.numel()):
+            call("coocc_maxpool2d_rows", ptr(x2d), C, BN, Hc, Wc, C, ptr(out), C, None)
+        ctx.save_for_backward(x2d)
+        ctx.cfg = (BN, Hc, Wc)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (x2d,) = ctx.saved_tensors
+        BN, Hc, Wc = ctx.cfg
+        C = x2d.shape[1]
+        dout = dout.float().contiguous()
+        dx = torch.empty_like(x2d)
+        with _lib.TIMER.region("k_maxpool2d_rows_bwd", 36.0 * dx.numel()):
+            call("coocc_maxpool2d_rows_bwd", ptr(x2d), C, ptr(dout), C, BN, Hc, Wc, C, ptr(dx), C)
+        return dx, None
+
+
+def maxpool_rows(x2d, geom):
+    """-> (pooled rows, (BN, Hp, Wp, 1)) of rows with geom (BN, Hc, Wc, 1)."""
+    BN, Hc, Wc = geom[:3]
+    return MaxPoolRowsFn.apply(x2d, (BN, Hc, Wc)), (BN, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1, 1)
+
+
+def deconv2d_bn_rows(x2d, up, bn, s, relu=True, sync=None):
+    """``deconv_bn_rows`` for a 2-D deblock -- nn.ConvTranspose2d(kernel = stride = s) -> BN2d -> ReLU (second_fpn.py:44-65) -- on
+    the COARSE rows [M, Cin] -> [M, s*s*Cout], child (kh, kw) of a coarse pixel at columns (kh*s + kw)*Cout ..: the weight
+    [Cin,Cout,s,s] is taken as a differentiable view in ``image_encoder.deconv2d_weight``'s layout, so its gradient lands in the
+    module's parameter; batch statistics over the [M*s*s, Cout] view are those of the upsampled map."""
+    cin, cout = up.weight.shape[:2]
+    assert tuple(up.weight.shape[2:]) == (s, s), "deconv kernel %s is not (%d,%d)" % (tuple(up.weight.shape[2:]), s, s)
+    w = up.weight.permute(2, 3, 1, 0).reshape(s * s * cout, cin)
+    b = up.bias.repeat(s * s) if up.bias is not None else None
+    n = x2d.shape[0]
+    if bn is not None and bn.training:
+        y = linear_rows(x2d, w, b, relu=False)
+        y = BatchNormRowsFn.apply(y.view(n * s * s, cout), bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync))
+        return y.view(n, s * s * cout)
+    scale = shift = None
+    if bn is not None:
+        from .core import fold_bn
+        sc, sh = fold_bn(bn, None)
+        scale, shift = sc.repeat(s * s).to(x2d.device).contiguous(), sh.repeat(s * s).to(x2d.device).contiguous()
+    return ConvRowsFn.apply(x2d.contiguous(), w, b, None, scale, shift, (1, n, 1, 1), _UNIT, _UNIT, _NOPAD, relu)

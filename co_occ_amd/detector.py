@@ -16,7 +16,8 @@ UPSTREAM of the hot path (out of scope) and are NOT re-implemented:
 mmdet / mmdet3d registries when those packages are importable, may be injected as ``nn.Module`` instances, and
 otherwise construction fails (``external_encoders=True`` defers the failure to the first call that needs them, for
 callers that feed ``precomputed=`` features or attach the encoders afterwards).  Opt-in exceptions: ``hip_image_encoder=True``
-builds ResNet / SECONDFPN config dicts from ``image_encoder`` (HIP engine, inference only), ``depth_net='hip'`` on the view
+builds ResNet / SECONDFPN config dicts from ``image_encoder`` (HIP engine; ``train_image_encoder=True`` also trains them there under
+``train()``), ``depth_net='hip'`` on the view
 transformer builds ``depth_net.DepthNet``.
 """
 import numpy as np
@@ -113,7 +114,7 @@ class COOCC_Ray(nn.Module):
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
                  train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, render_ssim=False, hip_image_encoder=False,
-                 **kwargs):
+                 train_image_encoder=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -149,14 +150,26 @@ class COOCC_Ray(nn.Module):
                                           "SparseLiDAREnc4x are); pass external_encoders=True to attach it yourself"
                                           % pts_middle_encoder.get("type"))
         # opt-in: ``img_backbone`` / ``img_neck`` config dicts of type ResNet / SECONDFPN are built from ``image_encoder`` -- the HIP
-        # engine, inference only -- instead of staying upstream (mmdet / mmdet3d); module instances are taken as they are
+        # engine -- instead of staying upstream (mmdet / mmdet3d); module instances are taken as they are.  ``train_image_encoder=True``
+        # on top of it: both modules' ``train_enabled`` is set, so under train() ``image_encoder()`` trains them on the HIP engine
+        # (frozen_stages / norm_eval as in mmdet); without it their train() forward raises
         self.hip_image_encoder = bool(hip_image_encoder)
+        self.train_image_encoder = bool(train_image_encoder)
         self.img_backbone = _build_upstream("backbone", img_backbone, external_encoders, self.hip_image_encoder)
         self.img_neck = _build_upstream("neck", img_neck, external_encoders, self.hip_image_encoder)
         if self.hip_image_encoder:
             from . import image_encoder
             if isinstance(self.img_backbone, image_encoder.ResNet) and isinstance(self.img_neck, image_encoder.SECONDFPN):
                 self.img_backbone.output_readers = image_encoder.NeckReaders(self.img_neck)
+        if self.train_image_encoder:
+            from . import image_encoder
+            if not (self.hip_image_encoder and isinstance(self.img_backbone, image_encoder.ResNet)
+                    and isinstance(self.img_neck, image_encoder.SECONDFPN)):
+                raise ValueError("%s: train_image_encoder=True trains this package's ResNet / SECONDFPN; pass hip_image_encoder=True "
+                                 "with img_backbone / img_neck config dicts of those types" % type(self).__name__)
+            for m in (self.img_backbone, self.img_neck):
+                m.train_enabled = True
+                m.train(m.training)
         self.pts_backbone = _build_upstream("backbone", pts_backbone, external_encoders)
         self.pts_neck = _build_upstream("neck", pts_neck, external_encoders)
         self.empty_idx, self.scale = empty_idx, scale

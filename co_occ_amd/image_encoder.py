@@ -1,5 +1,6 @@
 """``ResNet`` / ``SECONDFPN`` -- the 2-D image encoder of the ``coocc_nusc`` configs (``img_backbone`` / ``img_neck``) on the HIP
-engine, inference only and opt-in (``COOCC_Ray(hip_image_encoder=True)``).  Mirrors of mmdet 2.14's ``ResNet``
+engine, opt-in (``COOCC_Ray(hip_image_encoder=True)``); training is a second opt-in (``train_enabled`` on both
+modules, ``COOCC_Ray(train_image_encoder=True)``; the section "Training" below).  Mirrors of mmdet 2.14's ``ResNet``
 (depth 50 / 101, Bottleneck, ``style='pytorch'``) and mmdet3d's ``SECONDFPN`` (mmdet3d/models/necks/second_fpn.py): same constructor
 kwargs, ``forward`` signatures and state_dict keys (``conv1.weight``, ``bn1.*``, ``layer{i}.{j}.conv{1,2,3}.weight``,
 ``layer{i}.{j}.bn{1,2,3}.*``, ``layer{i}.0.downsample.{0.weight,1.*}``: 318 / 624 entries; ``deblocks.{i}.0.weight``,
@@ -17,7 +18,18 @@ the child scatter of ``coocc_fpn_sum``.  Each deblock writes its slice of ONE [B
 At the boundary the modules take and return the reference's [BN,C,H,W] tensors: zero-copy channels-last views that remember their
 Rows, so ``SECONDFPN.forward`` converts nothing and ``DepthNet.forward`` finds channels-last memory.  The classes live in their own
 registries (``IMAGE_BACKBONES`` / ``IMAGE_NECKS``), never in ``registry.BACKBONES`` / ``NECKS``: nothing builds them by default.
-``train()`` forwards raise; CPU tensors are refused; there is no eager-PyTorch fallback.
+CPU tensors are refused; there is no eager-PyTorch fallback.
+
+Training.  ``train_enabled`` is False by default and a ``train()`` forward then raises.  With it on (set it, then call ``train()``),
+``ResNet.train(mode)`` follows mmdet 2.14 -- ``frozen_stages >= 0`` puts ``conv1`` / ``bn1`` and stages 1..frozen_stages in eval and
+takes their parameters out of the gradient, ``norm_cfg['requires_grad']=False`` freezes the BN affine parameters, ``norm_eval=True``
+puts every BN in eval -- and the ``train()`` forward is differentiable in every parameter that requires a gradient: the frozen prefix
+runs the inference path above under ``no_grad`` (fused stem kernel, folded BN); every later Bottleneck layer is an
+``autograd.conv_bn_rows`` layer (``ConvRowsFn`` + ``BatchNormRowsFn``, each BN in its own mode, residual + ReLU in ``bn3``), the
+unfrozen stem is ``StemConvFn`` -> BN -> ``MaxPoolRowsFn`` (csrc/img_stem_train.hip), a deconvolution deblock is the pointwise GEMM on
+a differentiable view of its weight + ``FpnSumFn``'s child scatter, and the levels meet in ``torch.cat``.  The modules still return
+[BN,C,H,W] views of channels-last rows, now attached to the graph.  An eval-mode BN whose affine parameters require a gradient is
+refused (the folded epilogue would give them none); the image gets no gradient; ``with_cp`` stays ignored.
 """
 import ctypes
 
@@ -78,9 +90,50 @@ def bchw_to_rows(x):
 
 
 def _eval_only(module):
-    if module.training:
-        raise NotImplementedError("%s: the train() forward (batch statistics, dgrad / wgrad) is not built for the image encoder; "
-                                  "call .eval()" % type(module).__name__)
+    if module.training and not getattr(module, "train_enabled", False):
+        raise NotImplementedError("%s: training on the HIP engine is opt-in: set %s.train_enabled = True and call .train() again "
+                                  "(COOCC_Ray(hip_image_encoder=True, train_image_encoder=True)), or call .eval()"
+                                  % (type(module).__name__, type(module).__name__))
+
+
+def _ag():
+    from . import autograd
+    return autograd
+
+
+def _bns(module):
+    return [m for m in module.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+
+
+def _check_trainable_norms(module):
+    """An eval-mode BN is folded into its convolution's epilogue, which gives gamma / beta no gradient: refuse the combination
+    instead of leaving a silent zero."""
+    for m in _bns(module):
+        if not m.training and any(p is not None and p.requires_grad for p in (m.weight, m.bias)):
+            raise NotImplementedError("%s: a BatchNorm in eval mode whose weight / bias require a gradient (norm_eval=True with "
+                                      "norm_cfg requires_grad=True) is not built: the folded epilogue gives them none; freeze them "
+                                      "(requires_grad=False) or train the norm" % type(module).__name__)
+
+
+def _freeze(module):
+    module.eval()
+    for p in module.parameters():
+        p.requires_grad = False
+
+
+def bchw_to_rows2d(x):
+    """[BN,C,H,W] tensor (attached to a graph or not) -> (contiguous rows [BN*H*W, C], (BN, H, W, 1)); a view when the memory is
+    channels-last (what this file's modules return), one differentiable copy otherwise."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError("expected a [B*N,C,H,W] tensor")
+    if not x.is_cuda:
+        raise _lib.CooccError("co_occ_amd modules run on the GPU only (no CPU fallback)")
+    B, C, H, W = x.shape
+    return x.float().permute(0, 2, 3, 1).reshape(B * H * W, C), (B, H, W, 1)
+
+
+def rows2d_as_bchw(t, geom):
+    return t.view(geom[0], geom[1], geom[2], t.shape[1]).permute(0, 3, 1, 2)
 
 
 def _bn2d(norm_cfg, n, what):
@@ -154,7 +207,8 @@ def _c3(weight, bn, stride=1):
     return PackedConv(weight.detach().unsqueeze(-1), bn=bn, kernel=(3, 3, 1), strides=(stride, stride, 1), pads=(1, 1, 0))
 
 
-_IGNORED = ("pretrained", "init_cfg", "frozen_stages", "norm_eval", "with_cp", "zero_init_residual")
+# accepted and inert; ``frozen_stages``, ``norm_eval`` and ``norm_cfg['requires_grad']`` act under ``train_enabled`` only
+_IGNORED = ("pretrained", "init_cfg", "with_cp", "zero_init_residual")
 
 
 @IMAGE_BACKBONES.register_module()
@@ -228,22 +282,104 @@ class ResNet(nn.Module):
         # ``out_indices``; the detector points it at the neck's ``reader_packs``): their H2 operands come from the last epilogue
         self.output_readers = None
         self._packs = PackCache(self)
+        # training (opt-in).  With ``train_enabled`` on, ``train(mode)`` follows mmdet 2.14 (_freeze_stages + norm_eval) and the
+        # train() forward is differentiable in every parameter that requires a gradient; set it, then call ``train()``
+        self.train_enabled = False
+        self.frozen_stages, self.norm_eval = int(frozen_stages), bool(norm_eval)
+        self.norm_requires_grad = bool((norm_cfg or {}).get("requires_grad", True))
+        self._prefix_packs = PackCache(self)
 
     def init_weights(self, pretrained=None):
         """Loading ``pretrained`` / ``init_cfg`` checkpoints is the caller's (``load_state_dict``); torch's default initialisation
         is left alone."""
 
+    def _frozen_modules(self):
+        """The frozen prefix of mmdet's ``_freeze_stages``: the stem for ``frozen_stages >= 0``, then stages 1..frozen_stages."""
+        if self.frozen_stages < 0:
+            return []
+        return [self.conv1, self.bn1] + [getattr(self, name) for name in self.res_layers[:self.frozen_stages]]
+
+    def train(self, mode=True):
+        super().train(mode)
+        if not getattr(self, "train_enabled", False):
+            return self
+        for m in self._frozen_modules():                      # resnet.py _freeze_stages
+            _freeze(m)
+        if not self.norm_requires_grad:                       # build_norm_layer(requires_grad=False)
+            for m in _bns(self):
+                for p in m.parameters():
+                    p.requires_grad = False
+        if mode and self.norm_eval:
+            for m in _bns(self):
+                m.eval()
+        return self
+
+    def _packed_prefix(self):
+        """The inference packs of the frozen prefix alone (the trained layers are packed on the device every step)."""
+        n = min(max(self.frozen_stages, 0), len(self.res_layers))
+
+        def build():
+            layers = [[self._block_packs(b) for b in getattr(self, name)] for name in self.res_layers[:n]]
+            return dict(stem=stem_pack(self.conv1, self.bn1), layers=layers)
+        return self._prefix_packs.get_modules(tuple(self._frozen_modules()), build)
+
+    @staticmethod
+    def _block_packs(b):
+        ds = b.downsample
+        return dict(c1=_pw(b.conv1.weight, b.bn1), c2=_c3(b.conv2.weight, b.bn2, b.stride), c3=_pw(b.conv3.weight, b.bn3),
+                    ds=_pw(ds[0].weight, ds[1], b.stride) if ds is not None else None)
+
+    @staticmethod
+    def _run_block(h, b, nxt):
+        t = conv_rows(h, b["c1"], relu=True, twin_for=(b["c2"],))
+        t = conv_rows(t, b["c2"], relu=True, twin_for=(b["c3"],))
+        idn = conv_rows(h, b["ds"], relu=False) if b["ds"] is not None else h
+        return conv_rows(t, b["c3"], relu=True, res=idn, twin_for=nxt)
+
+    def forward_train(self, img):
+        """The train() forward: img [BN,3,H,W] -> per entry of ``out_indices`` (rows [BN*H_i*W_i, C_i], (BN, H_i, W_i, 1)), attached to
+        the graph.  The frozen prefix (stem + stages 1..frozen_stages, all in eval mode without gradients) runs the inference path
+        under no_grad -- fused stem kernel, folded BN --; every later layer is a ``conv_bn_rows`` layer with its BN in its own mode."""
+        ag = _ag()
+        if torch.is_tensor(img) and img.requires_grad:
+            raise NotImplementedError("ResNet: a gradient with respect to the image is not built")
+        if not torch.is_tensor(img) or img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError("image encoder: expected a [B*N,3,H,W] image tensor")
+        if not img.is_cuda:
+            raise _lib.CooccError("co_occ_amd modules run on the GPU only (no CPU fallback)")
+        _check_trainable_norms(self)
+        outs = {}
+        nf = min(max(self.frozen_stages, 0), len(self.res_layers))
+        if self.frozen_stages >= 0:
+            with torch.no_grad():
+                p = self._packed_prefix()
+                r = stem_rows(img, p["stem"], relu=True, pool=True)
+                for i, blocks in enumerate(p["layers"]):
+                    for b in blocks:
+                        r = self._run_block(r, b, ())
+                    outs[i] = (r.t, (r.B, r.X, r.Y, 1))
+            h, g = r.t, (r.B, r.X, r.Y, 1)
+        else:
+            h, g = ag.stem_conv_bn_rows(img, self.conv1, self.bn1, relu=True)
+            h, g = ag.maxpool_rows(h, g)
+        for i in range(nf, len(self.res_layers)):
+            for b in getattr(self, self.res_layers[i]):
+                s = (b.stride, b.stride, 1)
+                w1, w3 = b.conv1.weight.flatten(1), b.conv3.weight.flatten(1)
+                t, _ = ag.conv_bn_rows(h, w1, g, bn=b.bn1, relu=True)
+                t, go = ag.conv_bn_rows(t, b.conv2.weight.unsqueeze(-1), g, bn=b.bn2, stride=s, pad=(1, 1, 0), relu=True)
+                idn = h
+                if b.downsample is not None:
+                    wd = b.downsample[0].weight
+                    wd = wd.flatten(1) if b.stride == 1 else wd.unsqueeze(-1)
+                    idn, _ = ag.conv_bn_rows(h, wd, g, bn=b.downsample[1], stride=s, pad=0, relu=False)
+                h, g = ag.conv_bn_rows(t, w3, go, bn=b.bn3, relu=True, res2d=idn)
+            outs[i] = (h, g)
+        return [outs[i] for i in self.out_indices]
+
     def _packed(self):
         def build():
-            layers = []
-            for name in self.res_layers:
-                blocks = []
-                for b in getattr(self, name):
-                    ds = b.downsample
-                    blocks.append(dict(c1=_pw(b.conv1.weight, b.bn1), c2=_c3(b.conv2.weight, b.bn2, b.stride),
-                                       c3=_pw(b.conv3.weight, b.bn3),
-                                       ds=_pw(ds[0].weight, ds[1], b.stride) if ds is not None else None))
-                layers.append(blocks)
+            layers = [[self._block_packs(b) for b in getattr(self, name)] for name in self.res_layers]
             return dict(stem=stem_pack(self.conv1, self.bn1), layers=layers)
         return self._packs.get_modules((self,), build)
 
@@ -253,8 +389,10 @@ class ResNet(nn.Module):
 
     def forward_rows(self, img, readers=None):
         """img [BN,3,H,W] -> one Rows [BN, H_i, W_i, 1] per entry of ``out_indices``.  ``readers``: per entry, the layers outside this
-        module that read it next (default: ``output_readers()``)."""
+        module that read it next (default: ``output_readers()``).  The inference path: under train() use ``forward_train``."""
         _eval_only(self)
+        if self.training:
+            raise NotImplementedError("ResNet.forward_rows is the inference path (folded BN); under train() call forward_train, or .eval()")
         p = self._packed()
         layers = p["layers"]
         if readers is None and self.output_readers is not None:
@@ -271,17 +409,17 @@ class ResNet(nn.Module):
                     nxt = self._readers_of(layers[i + 1][0]) if i + 1 < len(layers) else ()
                     if readers is not None and i in self.out_indices:
                         nxt += tuple(readers[self.out_indices.index(i)])
-                t = conv_rows(h, b["c1"], relu=True, twin_for=(b["c2"],))
-                t = conv_rows(t, b["c2"], relu=True, twin_for=(b["c3"],))
-                idn = conv_rows(h, b["ds"], relu=False) if b["ds"] is not None else h
-                h = conv_rows(t, b["c3"], relu=True, res=idn, twin_for=nxt)
+                h = self._run_block(h, b, nxt)
             if i in self.out_indices:
                 outs.append(h)
         return [outs[sorted(self.out_indices).index(i)] for i in self.out_indices]
 
     def forward(self, x):
-        """[BN,3,H,W] -> tuple of [BN,C_i,H_i,W_i]: zero-copy channels-last views that remember their Rows."""
+        """[BN,3,H,W] -> tuple of [BN,C_i,H_i,W_i]: zero-copy channels-last views that remember their Rows (eval), or that are
+        attached to the graph (train() with ``train_enabled``)."""
         _eval_only(self)
+        if self.training:
+            return tuple(rows2d_as_bchw(t, g) for t, g in self.forward_train(x))
         return tuple(rows_as_bchw(r) for r in self.forward_rows(x))
 
 
@@ -329,6 +467,49 @@ class SECONDFPN(nn.Module):
         if init_cfg is None:
             self.init_cfg = [dict(type='Kaiming', layer='ConvTranspose2d'), dict(type='Constant', layer='NaiveSyncBatchNorm2d', val=1.0)]
         self._packs = PackCache(self)
+        # training (opt-in, as ``ResNet.train_enabled``): the train() forward is differentiable, every BN in its own mode
+        self.train_enabled = False
+        self.norm_requires_grad = bool((norm_cfg or {}).get("requires_grad", True))
+
+    def train(self, mode=True):
+        super().train(mode)
+        if getattr(self, "train_enabled", False) and not self.norm_requires_grad:        # build_norm_layer(requires_grad=False)
+            for m in _bns(self):
+                for p in m.parameters():
+                    p.requires_grad = False
+        return self
+
+    def deblock_train(self, i, x2d, geom):
+        """Deblock i on differentiable rows -> (rows [BN*H*W, out_channels[i]], (BN, H, W, 1)): a convolution is a ``conv_bn_rows``
+        layer, a deconvolution the pointwise GEMM Cin -> s*s*Cout on a view of the module's weight + the child scatter of
+        ``FpnSumFn`` (one level)."""
+        ag = _ag()
+        (kind, k), blk, oc = self.levels[i], self.deblocks[i], self.out_channels[i]
+        up, bn = blk[0], blk[1]
+        B, H, W, _ = geom
+        if kind == "conv":
+            if H % k or W % k:
+                raise ValueError("SECONDFPN: a %d x %d level is not a multiple of its stride-%d convolution" % (H, W, k))
+            w = up.weight.flatten(1) if k == 1 else up.weight.unsqueeze(-1)
+            return ag.conv_bn_rows(x2d, w, geom, bn=bn, bias=up.bias, stride=(k, k, 1), pad=0, relu=True)
+        if k == 1:
+            return ag.conv_bn_rows(x2d, up.weight[:, :, 0, 0].t(), geom, bn=bn, bias=up.bias, relu=True)
+        y = ag.deconv2d_bn_rows(x2d, up, bn, k, relu=True)
+        fine = (B, H * k, W * k, 1)
+        return ag.fpn_sum_rows([y], [k], oc, fine), fine
+
+    def forward_train(self, xs):
+        """[(rows, geom)] per level -> (rows [BN*H*W, sum(out_channels)], geom): the deblocks, then ``torch.cat`` over levels."""
+        _check_trainable_norms(self)
+        assert len(xs) == len(self.in_channels)
+        for (t, g), c in zip(xs, self.in_channels):
+            if t.shape[1] != c:
+                raise ValueError("SECONDFPN: a level has %d channels, built for %d" % (t.shape[1], c))
+        ups = [self.deblock_train(i, t, g) for i, (t, g) in enumerate(xs)]
+        if len({g for _, g in ups}) != 1:
+            raise ValueError("SECONDFPN: level sizes differ after up/down-sampling: inputs %s give %s (image sides must be multiples "
+                             "of 32)" % ([g[1:3] for _, g in xs], [g[1:3] for _, g in ups]))
+        return (torch.cat([t for t, _ in ups], 1) if len(ups) > 1 else ups[0][0]), ups[0][1]
 
     def _packed(self):
         def build():
@@ -376,8 +557,11 @@ class SECONDFPN(nn.Module):
         """One Rows [BN, H_i, W_i, 1] per level -> Rows [BN, H, W, 1] with sum(out_channels) channels: every deblock writes its
         channel slice of the one buffer."""
         _eval_only(self)
+        if self.training:
+            raise NotImplementedError("SECONDFPN.forward_rows is the inference path (folded BN); under train() call forward_train, or "
+                                      ".eval()")
         assert len(xs) == len(self.in_channels)
-        sizes = [self.out_size(i, x.X, x.Y) for i, x in enumerate(xs)]
+        sizes =[self.out_size(i, x.X, x.Y) for i, x in enumerate(xs)]
         if len(set(sizes)) != 1 or min(sizes[0]) < 1 or len({x.B for x in xs}) != 1:
             raise ValueError("SECONDFPN: level sizes differ after up/down-sampling: inputs %s give %s (image sides must be multiples "
                              "of 32)" % ([(x.X, x.Y) for x in xs], sizes))
@@ -394,8 +578,12 @@ class SECONDFPN(nn.Module):
         return Rows(buf, B, H, W, 1, Ct)
 
     def forward(self, x):
-        """list of [BN,C_i,H_i,W_i] -> [cat(ups, 1)] (second_fpn.py:75-91): a zero-copy view of channels-last rows."""
+        """list of [BN,C_i,H_i,W_i] -> [cat(ups, 1)] (second_fpn.py:75-91): a zero-copy view of channels-last rows.  Under train()
+        (``train_enabled``) the inputs are read without a copy when their memory is channels-last, and the view is attached to the
+        graph."""
         _eval_only(self)
+        if self.training:
+            return [rows2d_as_bchw(*self.forward_train([bchw_to_rows2d(t) for t in x]))]
         return [rows_as_bchw(self.forward_rows([bchw_to_rows(t) for t in x]))]
 
 
@@ -423,5 +611,6 @@ class NeckReaders:
 
 
 def run_image_encoder(backbone, neck, img):
-    """``neck(backbone(img))`` on Rows end to end: the backbone's last layers write the H2 operands of the neck's deblocks."""
+    """``neck(backbone(img))`` on Rows end to end: the backbone's last layers write the H2 operands of the neck's deblocks.  The
+    inference path: under train() call the modules (``neck(backbone(img))``)."""
     return neck.forward_rows(backbone.forward_rows(img, readers=neck.reader_packs()))

@@ -74,7 +74,8 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
 
 
 def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False,
-                        device_occ_losses=False, hip_depth_net=False, train_depth_net=False, hip_image_encoder=False):
+                        device_occ_losses=False, hip_depth_net=False, train_depth_net=False, hip_image_encoder=False,
+                        train_image_encoder=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -93,8 +94,13 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     the HIP engine (``depth_net.DepthNet``) instead of the reference's class and mmcv's DCN; ``train_depth_net=True`` (with
     ``hip_depth_net=True``) registers it with its ``train_depth_net`` option on by default as well, so the module also trains on the
     HIP engine under ``train()``.  ``hip_image_encoder=True`` registers ``image_encoder.ResNet`` / ``image_encoder.SECONDFPN`` (the 2-D
-    image backbone and neck on the HIP engine, inference only) under the reference names ``ResNet`` / ``SECONDFPN``, so an unchanged
-    config builds them as ``img_backbone`` / ``img_neck``.  Returns False when mmdet / mmdet3d are not importable."""
+    image backbone and neck on the HIP engine) under the reference names ``ResNet`` / ``SECONDFPN``, so an unchanged config builds
+    them as ``img_backbone`` / ``img_neck``; ``train_image_encoder=True`` (with ``hip_image_encoder=True``) registers them with their
+    ``train_enabled`` option on, so the reference's own detector trains them on the HIP engine under ``train()`` (``frozen_stages`` /
+    ``norm_eval`` as in mmdet).  Returns False when mmdet / mmdet3d are not importable."""
+    if train_image_encoder and not hip_image_encoder:
+        raise ValueError("register_into_mmdet: train_image_encoder=True trains this package's ResNet / SECONDFPN; pass "
+                         "hip_image_encoder=True")
     if train_depth_net and not hip_depth_net:
         raise ValueError("register_into_mmdet: train_depth_net=True trains this package's DepthNet; pass hip_depth_net=True")
     if device_occ_losses and not detectors:
@@ -126,8 +132,9 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
         m3b.NECKS.register_module(name="ViewTransformerLiftSplatShootVoxel", force=True, module=hip_depth_net_view_transformer(train_depth_net))
     if hip_image_encoder:
         from . import image_encoder
-        m3b.BACKBONES.register_module(name="ResNet", force=True, module=image_encoder.ResNet)
-        m3b.NECKS.register_module(name="SECONDFPN", force=True, module=image_encoder.SECONDFPN)
+        bb, nk = training_image_encoder() if train_image_encoder else (image_encoder.ResNet, image_encoder.SECONDFPN)
+        m3b.BACKBONES.register_module(name="ResNet", force=True, module=bb)
+        m3b.NECKS.register_module(name="SECONDFPN", force=True, module=nk)
     if detectors and (train_lidar_trunk or train_sparse_encoder_hd):
         mb.DETECTORS.register_module(name="COOCC_Ray_L", force=True,
                                      module=trunk_training_detector(train_lidar_trunk, train_sparse_encoder_hd))
@@ -175,6 +182,23 @@ def hip_depth_net_view_transformer(train_depth_net=False):
             super().__init__(*args, depth_net=depth_net, train_depth_net=train_depth_net, **kwargs)
     ViewTransformerLiftSplatShootVoxel.__qualname__ = "ViewTransformerLiftSplatShootVoxel"
     return ViewTransformerLiftSplatShootVoxel
+
+
+def training_image_encoder():
+    """(``image_encoder.ResNet``, ``image_encoder.SECONDFPN``) with ``train_enabled`` on (what
+    ``register_into_mmdet(hip_image_encoder=True, train_image_encoder=True)`` puts into mmdet3d's registries: upstream's constructor
+    signatures, the differentiable forward and mmdet's stage freezing under ``train()``)."""
+    from . import image_encoder
+
+    def enabled(base):
+        class _Enabled(base):
+            def __init__(self, *args, **kwargs):
+                super().__init__(*args, **kwargs)
+                self.train_enabled = True
+                self.train(self.training)
+        _Enabled.__name__ = _Enabled.__qualname__ = base.__name__
+        return _Enabled
+    return enabled(image_encoder.ResNet), enabled(image_encoder.SECONDFPN)
 
 
 def training_sparse_encoder_hd():

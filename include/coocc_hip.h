@@ -985,6 +985,29 @@ int coocc_dropout_rows(const float* x, const uint8_t* mask, int64_t M, int C, fl
 int coocc_img_stem(const float* img, int BN, int H, int W, const float* w, const float* scale, const float* bias, int C0, int relu,
                    int pool, float* out, int out_stride, void* out_h2_twin, void* stream);
 
+/* ---- training of the image encoder's stem (image_encoder.ResNet.train_enabled, csrc/img_stem_train.hip).  fp32, no atomics, the
+ * same bits from run to run. */
+/* MaxPool2d(3, stride 2, padding 1) on channels-last rows x [BN*Hc*Wc][x_stride] (C channels) -> out [BN*Hp*Wp][out_stride] with
+ * Hp = (Hc-1)/2 + 1, Wp = (Wc-1)/2 + 1; out_h2_twin: optional H2 copy [rows][C] (C % 32 == 0).  The maximum is `v > m ? v : m` from
+ * -inf over the window positions inside the map, in row-major window order: padding is never a candidate, and the bits are those
+ * of coocc_img_stem(pool = 1) on the same pre-pool map.  Non-finite inputs are out of scope.  C, strides % 4 == 0; 16-byte aligned;
+ * BN*Hc*Wc < 2^31. */
+int coocc_maxpool2d_rows(const float* x, int x_stride, int BN, int Hc, int Wc, int C, float* out, int out_stride, void* out_h2_twin,
+                         void* stream);
+/* Its backward from the pre-pool map x (no index tensor): dx[BN*Hc*Wc][dx_stride] = sum of dy [BN*Hp*Wp][dy_stride] over the (at
+ * most 2 x 2) windows whose FIRST maximum in row-major window order (strict >, torch's tie rule) is that pixel, added in ascending
+ * window order.  Every dx element (C channels per row) is written exactly once, zeros included. */
+int coocc_maxpool2d_rows_bwd(const float* x, int x_stride, const float* dy, int dy_stride, int BN, int Hc, int Wc, int C, float* dx,
+                             int dx_stride, void* stream);
+/* Weight gradient of the stem convolution: dw [147][C0] (row (ci*7 + ky)*7 + kx, the layout of coocc_img_stem's w) from img
+ * [BN][3][H][W] (fp32 NCHW) and dy [BN*Hc*Wc][dy_stride], the gradient of the raw convolution output; zero padding as in the forward.
+ * Plain fp32 FMAs.  The map is cut into 8 x 16 tiles; P = min(tiles, 512) workgroups walk tiles g, g + P, ... (shape-dependent only),
+ * each writes one partial [147][C0] into ws, and a second kernel adds the partials in ascending order.  ws: at least
+ * coocc_img_stem_wgrad_ws(BN, H, W) bytes, 16-byte aligned.  C0 == 64; BN*Hc*Wc < 2^31. */
+size_t coocc_img_stem_wgrad_ws(int BN, int H, int W);
+int coocc_img_stem_wgrad(const float* img, int BN, int H, int W, const float* dy, int dy_stride, int C0, float* dw, void* ws,
+                         size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
