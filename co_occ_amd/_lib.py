@@ -190,6 +190,10 @@ SIGNATURES = {
     "coocc_occ_loss_ws": (Z, [L, I]),
     "coocc_occ_loss_fwd": (I, [P, L, I, I, P, P, I, I, I, P, P, I, P, P, P, P, Z, P]),
     "coocc_occ_loss_bwd": (I, [P, L, I, I, P, P, I, P, P, P, P, I, P]),
+    "coocc_depth_labels": (I, [P, I, I, I, I, F, F, I, P, P, P]),
+    "coocc_depth_bce_ws": (Z, [L, I]),
+    "coocc_depth_bce": (I, [P, P, I, I, I, I, F, P, P, P, Z, P]),
+    "coocc_depth_bce_bwd": (I, [P, P, I, I, I, I, F, P, P, P, P]),
     "coocc_nbr_table2d": (I, [I, I, I, I, P, P]),
     "coocc_dcn_cols": (I, [P, I, P, I, I, I, I, I, I, I, I, P, P]),
     "coocc_se_gate2": (I, [P, I, I, I, I, P, P, P, P, P]),

@@ -701,6 +701,35 @@ class OccLossFn(torch.autograd.Function):
         return drows, None, None, None, None
 
 
+class DepthLossFn(torch.autograd.Function):
+    """-> 0-dim tensor = ``weight * sum / max(1, n_fg)`` of ``ViewTransformerLiftSplatShootVoxel.get_depth_loss`` ('bce') for depth
+    probabilities [B*N,D,h,w] (any strides / dtype: read as contiguous float32) against int32 ``labels`` [B*N,h,w] (0 = no
+    foreground, 1..D = bin 0..D-1; ``losses.depth_labels_device``).  Two launches forward, ONE coocc_depth_bce_bwd call backward on the
+    saved (sum, n_fg) pair; the gradient comes back in the input's shape and dtype."""
+
+    @staticmethod
+    def forward(ctx, preds, labels, weight):
+        BN, D, h, w = preds.shape
+        dev = preds.device
+        p = preds.detach().float().contiguous()
+        loss = torch.empty((), device=dev, dtype=_F32)
+        stats = torch.empty(2, device=dev, dtype=torch.float64)             # COOCC_DEPTH_BCE_STATS
+        ws = stream_buffer(dev, "s:depth_loss", (int(_lib.load().coocc_depth_bce_ws(BN * h * w, D)) + 3) // 4)
+        call("coocc_depth_bce", ptr(p, _F32), ptr(labels, torch.int32), BN, D, h, w, float(weight), ptr(loss), ptr(stats), ptr(ws),
+             ws.numel() * 4)
+        ctx.save_for_backward(p, labels, stats)
+        ctx.cfg = (BN, D, h, w, float(weight), preds.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        p, labels, stats = ctx.saved_tensors
+        BN, D, h, w, weight, dtype = ctx.cfg
+        dp = torch.empty(BN, D, h, w, device=p.device, dtype=_F32)
+        call("coocc_depth_bce_bwd", ptr(p), ptr(labels), BN, D, h, w, weight, ptr(stats), ptr(gl.float().reshape(1).contiguous()), ptr(dp))
+        return (dp if dtype == _F32 else dp.to(dtype)), None, None
+
+
 def render_block_train(sigma_head, rgb_head, feats2d, grid, gemo, scale=16):
     """Differentiable render block: feats2d [X*Y*Z, C] rows -> (rgbs, depths).  The per-voxel heads run through
     ConvRowsFn (Linear+ReLU layers), so gradients reach the voxel features and both MLPs.  ``rgb_head=None``: the

@@ -114,7 +114,7 @@ class COOCC_Ray(nn.Module):
                  pts_voxel_encoder=None, pts_middle_encoder=None, img_backbone=None, img_neck=None,
                  pts_backbone=None, pts_neck=None, external_encoders=False, render_eval=False, sparse_encoder_hd=False,
                  train_lidar_trunk=False, train_sparse_encoder_hd=False, device_occ_losses=False, render_ssim=False, hip_image_encoder=False,
-                 train_image_encoder=False, **kwargs):
+                 train_image_encoder=False, device_depth_loss=False, **kwargs):
         super().__init__()
         self.ignored_cfg_keys = sorted(kwargs)      # train_cfg / test_cfg / pretrained / img_bev_encoder_* ...
         self.external_encoders = external_encoders
@@ -198,6 +198,12 @@ class COOCC_Ray(nn.Module):
         self.device_occ_losses = bool(device_occ_losses)
         if self.pts_bbox_head is not None:
             self.pts_bbox_head.device_losses = self.device_occ_losses
+        # opt-in: the view transformer's get_depth_loss (``loss_depth``) computes its labels, the BCE and the gradient on the device
+        # (losses.depth_loss_device: no host read, bitwise reproducible) instead of eager torch.  On, it switches the module's own
+        # ``device_depth_loss`` on; off, the module keeps what its config set.  Detectors without a view transformer ignore it
+        self.device_depth_loss = bool(device_depth_loss)
+        if self.img_view_transformer is not None and self.device_depth_loss:
+            self.img_view_transformer.device_depth_loss = True
         self.occ_fuser = registry.build_fusion_layer(occ_fuser) if occ_fuser is not None else None
         self.semantic_encoder = registry.build_backbone(semantic_encoder)
         self.semantic_neck = registry.build_neck(semantic_neck)
@@ -667,7 +673,8 @@ class COOCC_Ray(nn.Module):
     # ------------------------------------------------------------------ training (coocc_ray.py:313-518)
     def forward_train(self, points=None, img_metas=None, img_inputs=None, gt_occ=None, points_occ=None, visible_mask=None,
                       gt_depths=None, precomputed=None, generator=None, **kwargs):
-        """Reference signature; returns the reference's loss dict: ``loss_depth`` (DepthNet BCE, upstream torch),
+        """Reference signature; returns the reference's loss dict: ``loss_depth`` (DepthNet BCE: upstream torch, or with
+        ``device_depth_loss`` the HIP kernels of ``losses.depth_loss_device`` -- no host read, bitwise reproducible),
         the OccHead losses ``loss_voxel_{ce,sem_scal,geo_scal,lovasz}_{c_0,fine}`` (co_occ_amd.losses), ``loss_norm``
         rescaling, and the render regulariser ``loss_depth_render`` / ``loss_rgb`` (camera branch :358-434) or
         ``loss_depth_render`` alone through ``get_frustum`` (LiDAR-only branch :436-496).  Everything between the

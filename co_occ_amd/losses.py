@@ -4,7 +4,8 @@ semantic / geometric scene-class affinity losses (P/utils/semkitti.py:65-149) an
 
 The functions below are host-side eager torch on the logits the HIP path produced, exactly as upstream; ``occ_loss_terms_device`` /
 ``pool_labels_device`` at the end of the file compute the same numbers and their gradient in HIP kernels (csrc/occ_loss.hip, opt-in
-through ``OccHead.device_losses``).  (The losses are a few reductions over
+through ``OccHead.device_losses``); ``depth_labels_device`` / ``depth_loss_device`` after them are the device form of the view
+transformer's DepthNet supervision (csrc/depth_loss.hip, opt-in through its ``device_depth_loss``).  (The losses are a few reductions over
 80 k coarse voxels / <= 8 x fine_topk fine points; they are downstream of the hot path)  Restated in
 vectorised form -- one softmax, one one-hot matmul for all per-class sums, one column-wise sort for all present classes
 -- instead of the reference's per-class Python loops; the arithmetic (sums, ratios, -log clamped at 100) is the same, so
@@ -193,3 +194,42 @@ def pool_labels_device(target_voxels, H, W, D, empty_idx=0, num_cls=17, dtype=to
     out = torch.empty(B, H, W, D, device=vol.device, dtype=torch.uint8)
     call("coocc_pool_labels", ptr(vol), B, H, W, D, ratio, int(empty_idx), int(num_cls), ptr(out))
     return out if dtype == torch.uint8 else out.to(dtype)
+
+
+# ----------------------------------------------------------------------------- the DepthNet depth loss on the device (csrc/depth_loss.hip)
+def _depth_maps(name, gt_depths, downsample):
+    """[B,N,H,W] (or [B*N,H,W]) depth maps -> the contiguous float32 [B*N,H,W] tensor the label kernel reads."""
+    if gt_depths.dim() not in (3, 4):
+        raise ValueError("%s: gt_depths %s is not [B,N,H,W]" % (name, tuple(gt_depths.shape)))
+    H, W = gt_depths.shape[-2:]
+    if H % downsample or W % downsample:
+        raise ValueError("%s: depth maps %d x %d are not a multiple of downsample = %d" % (name, H, W, downsample))
+    return gt_depths.reshape(-1, H, W).float().contiguous()
+
+
+def depth_labels_device(gt_depths, downsample, dbound, D):
+    """``ViewTransformerLiftSplatShootVoxel.get_downsampled_gt_depth`` as one HIP kernel: [B,N,H,W] metric depth -> (``vals`` [B*N,h,w]
+    float32, the eager function's bits; ``labels`` [B*N,h,w] int32: 0 = no foreground, 1..D = the one-hot's column + 1).  ``dbound`` =
+    ``grid_config['dbound']``; ``downsample``: a power of two from 1 to 32."""
+    _device_only("depth_labels_device", gt_depths)
+    from ._lib import call, ptr
+    ds = int(downsample)
+    g = _depth_maps("depth_labels_device", gt_depths, ds)
+    BN, H, W = g.shape
+    vals = torch.empty(BN, H // ds, W // ds, device=g.device, dtype=torch.float32)
+    labels = torch.empty(BN, H // ds, W // ds, device=g.device, dtype=torch.int32)
+    # the eager expression subtracts the Python (double) number dbound[0] - dbound[2] / 2 and divides by dbound[2], each as a float32
+    call("coocc_depth_labels", ptr(g), BN, H, W, ds, float(dbound[0] - dbound[2] / 2), float(dbound[2]), int(D), ptr(vals), ptr(labels))
+    return vals, labels
+
+
+def depth_loss_device(depth_preds, gt_depths, downsample, dbound, D, weight):
+    """``get_depth_loss`` ('bce') of ``depth_preds`` [B*N,D,h,w] against the depth maps ``gt_depths`` [B,N,H,W] as ONE differentiable
+    0-dim float32 tensor: HIP kernels forward (3 launches) and backward (1), no host read, bitwise reproducible.  Non-contiguous
+    ``depth_preds`` and non-float32 ``gt_depths`` are converted; the gradient has ``depth_preds``' shape."""
+    _device_only("depth_loss_device", depth_preds, gt_depths)
+    from .autograd import DepthLossFn
+    _, labels = depth_labels_device(gt_depths, downsample, dbound, D)
+    if depth_preds.dim() != 4 or tuple(depth_preds.shape) != (labels.shape[0], int(D), labels.shape[1], labels.shape[2]):
+        raise ValueError("depth_loss_device: depth_preds %s for labels %s and D = %d" % (tuple(depth_preds.shape), tuple(labels.shape), D))
+    return DepthLossFn.apply(depth_preds, labels, float(weight))

@@ -75,7 +75,7 @@ def build_detector(cfg, train_cfg=None, test_cfg=None, **overrides):
 
 def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_trunk=False, train_sparse_encoder_hd=False,
                         device_occ_losses=False, hip_depth_net=False, train_depth_net=False, hip_image_encoder=False,
-                        train_image_encoder=False):
+                        train_image_encoder=False, device_depth_loss=False):
     """Register our classes under the reference names into the real mmdet / mmdet3d registries (``force=True``).
 
     Default: the hot-path MODULES only (BiFuser_N, CustomResNet3D, FPN3D, OccHead, ViewTransformerLiftSplatShootVoxel and
@@ -97,7 +97,11 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     image backbone and neck on the HIP engine) under the reference names ``ResNet`` / ``SECONDFPN``, so an unchanged config builds
     them as ``img_backbone`` / ``img_neck``; ``train_image_encoder=True`` (with ``hip_image_encoder=True``) registers them with their
     ``train_enabled`` option on, so the reference's own detector trains them on the HIP engine under ``train()`` (``frozen_stages`` /
-    ``norm_eval`` as in mmdet).  Returns False when mmdet / mmdet3d are not importable."""
+    ``norm_eval`` as in mmdet).  ``device_depth_loss=True`` registers a ``ViewTransformerLiftSplatShootVoxel`` whose
+    ``device_depth_loss`` option is on by default (a subclass of whatever ``hip_depth_net`` / ``train_depth_net`` produced): the
+    reference's own detector calls its ``get_depth_loss``, which then computes the depth labels, the BCE and its gradient on the device
+    without a host read; with ``detectors=True`` ``COOCC_Ray`` and ``COOCC_Ray_L`` are registered with the option on by default as well
+    (on top of the ``device_occ_losses`` and trunk-training wrappers).  Returns False when mmdet / mmdet3d are not importable."""
     if train_image_encoder and not hip_image_encoder:
         raise ValueError("register_into_mmdet: train_image_encoder=True trains this package's ResNet / SECONDFPN; pass "
                          "hip_image_encoder=True")
@@ -141,7 +145,40 @@ def register_into_mmdet(detectors=False, sparse_encoder_hd=False, train_lidar_tr
     if detectors and device_occ_losses:
         for name in ("COOCC_Ray", "COOCC_Ray_L"):
             mb.DETECTORS.register_module(name=name, force=True, module=device_occ_losses_detector(mb.DETECTORS.module_dict[name]))
+    if device_depth_loss:
+        name = "ViewTransformerLiftSplatShootVoxel"
+        m3b.NECKS.register_module(name=name, force=True, module=device_depth_loss_view_transformer(m3b.NECKS.module_dict[name]))
+        if detectors:
+            for name in ("COOCC_Ray", "COOCC_Ray_L"):
+                mb.DETECTORS.register_module(name=name, force=True, module=device_depth_loss_detector(mb.DETECTORS.module_dict[name]))
     return True
+
+
+def device_depth_loss_view_transformer(base=None):
+    """``base`` (``ViewTransformerLiftSplatShootVoxel``, possibly already a ``hip_depth_net_view_transformer``) whose
+    ``device_depth_loss`` option is on by default (what ``register_into_mmdet(device_depth_loss=True)`` puts into mmdet3d's registry
+    under the reference name)."""
+    if base is None:
+        base = NECKS.get("ViewTransformerLiftSplatShootVoxel")
+
+    class _VT(base):
+        def __init__(self, *args, device_depth_loss=True, **kwargs):
+            super().__init__(*args, device_depth_loss=device_depth_loss, **kwargs)
+    _VT.__name__ = _VT.__qualname__ = base.__name__
+    return _VT
+
+
+def device_depth_loss_detector(base):
+    """``base`` (``COOCC_Ray`` / ``COOCC_Ray_L``, possibly already a ``device_occ_losses_detector`` / ``trunk_training_detector``)
+    whose ``device_depth_loss`` option is on by default (``register_into_mmdet(detectors=True, device_depth_loss=True)``)."""
+    if isinstance(base, str):
+        base = DETECTORS.get(base)
+
+    class _Det(base):
+        def __init__(self, *args, device_depth_loss=True, **kwargs):
+            super().__init__(*args, device_depth_loss=device_depth_loss, **kwargs)
+    _Det.__name__ = _Det.__qualname__ = base.__name__
+    return _Det
 
 
 def device_occ_losses_detector(base):

@@ -72,8 +72,12 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
     def __init__(self, loss_depth_weight=1.0, scale=16, point_cloud_range=None, loss_depth_type='bce',
                  grid_config=None, data_config=None, numC_input=512, numC_Trans=64, downsample=16,
                  accelerate=False, use_bev_pool=True, vp_megvii=False, vp_stero=False, cam_channels=27,
-                 loss_depth_reg_weight=0.0, use_voxel_net=False, depth_net=None, train_depth_net=False, **kwargs):
+                 loss_depth_reg_weight=0.0, use_voxel_net=False, depth_net=None, train_depth_net=False, device_depth_loss=False,
+                 **kwargs):
         super().__init__()
+        # opt-in: get_depth_loss computes the depth labels, the BCE and its gradient on the device (losses.depth_loss_device: no host
+        # read, bitwise reproducible) instead of eager torch
+        self.device_depth_loss = bool(device_depth_loss)
         if use_voxel_net:
             raise NotImplementedError("DepthAggregation (use_voxel_net) is not used by the coocc_nusc configs")
         if grid_config is None:
@@ -314,7 +318,8 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         vol_sum = (img_feat * depth_prob.sum(1, keepdim=True)).permute(0, 2, 3, 1)      # == volume.sum over D (:145)
         return bev_feat, depth_prob, geom, vol_sum
 
-    # ------------------------------------------------------------------ DepthNet supervision (upstream torch, eager)
+    # ------------------------------------------------------------------ DepthNet supervision (upstream torch, eager; with
+    # ``device_depth_loss`` get_depth_loss runs csrc/depth_loss.hip instead)
     def get_downsampled_gt_depth(self, gt_depths):
         """ViewTransformerLSSVoxel.py:30-56: [B,N,H,W] metric depth -> (bin values [B*N,h,w], one-hot [B*N*h*w, D]) with the
         nearest non-zero depth of every downsample x downsample patch."""
@@ -330,9 +335,13 @@ class ViewTransformerLiftSplatShootVoxel(nn.Module):
         return vals, onehot.float()
 
     def get_depth_loss(self, depth_labels, depth_preds):
-        """ViewTransformerLSSVoxel.py:58-98, 'bce' type (what the coocc_nusc configs set)."""
+        """ViewTransformerLSSVoxel.py:58-98, 'bce' type (what the coocc_nusc configs set).  ``device_depth_loss``: the same number and
+        its gradient from ``losses.depth_loss_device`` (HIP kernels, no host read)."""
         if self.loss_depth_type != 'bce':
             raise NotImplementedError("loss_depth_type %r: only 'bce' is used by the coocc_nusc configs" % self.loss_depth_type)
+        if self.device_depth_loss:
+            from .losses import depth_loss_device
+            return depth_loss_device(depth_preds, depth_labels, self.downsample, self.grid_config['dbound'], self.D, self.loss_depth_weight)
         _, labels = self.get_downsampled_gt_depth(depth_labels)
         preds = depth_preds.permute(0, 2, 3, 1).contiguous().view(-1, self.D)
         fg = labels.max(dim=1).values > 0.0

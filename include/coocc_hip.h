@@ -928,6 +928,27 @@ int coocc_occ_loss_fwd(const float* logits, int64_t P, int C, int ld, const uint
 int coocc_occ_loss_bwd(const float* logits, int64_t P, int C, int ld, const uint8_t* row_labels, const float* class_w, int empty_idx,
                        const double* stats, const float* lov_w, const float* gout, float* dlogits, int ldg, void* stream);
 
+/* ---- the DepthNet depth loss on the device (co_occ_amd/losses.py depth_loss_device, csrc/depth_loss.hip) */
+#define COOCC_DEPTH_BCE_STATS 2 /* doubles coocc_depth_bce saves for coocc_depth_bce_bwd: the fp64 sum, the foreground count */
+/* get_downsampled_gt_depth (ViewTransformerLSSVoxel.py:30-56): gt [BN][H][W] metric depth -> per pixel of the [BN][H/ds][W/ds] map
+ * m = the minimum of its ds x ds patch with exact zeros read as 1e5, vals = (m - c0) / step (two fp32 operations, a true division)
+ * and labels = (int)vals where 0 <= vals < D + 1, else 0.  Label 0 = no foreground, labels 1..D = bins 0..D-1.  ds: a power of two
+ * in 1..32 that divides H and W.  Every element of vals and labels is written. */
+int coocc_depth_labels(const float* gt, int BN, int H, int W, int ds, float c0, float step, int D, float* vals, int32_t* labels,
+                       void* stream);
+/* Bytes of workspace coocc_depth_bce needs for P = BN*h*w pixels of D bins (the per-workgroup fp64 partials). */
+size_t coocc_depth_bce_ws(int64_t P, int D);
+/* get_depth_loss, 'bce' (ViewTransformerLSSVoxel.py:58-98): prob [BN][D][h][w] contiguous, labels [BN][h][w] of coocc_depth_labels.
+ * Over the pixels with label > 0 the sum over d of -(y log p + (1 - y) log(1 - p)), y = (d + 1 == label), every logarithm clamped
+ * below at -100; fp32 terms, fp64 sums in a fixed order.  loss[0] = weight * sum / max(1, n_fg); stats[0] = sum, stats[1] = n_fg.
+ * Two launches, no host read, no allocation. */
+int coocc_depth_bce(const float* prob, const int32_t* labels, int BN, int D, int h, int w, float weight, float* loss, double* stats,
+                    void* ws, size_t ws_bytes, void* stream);
+/* dprob [BN][D][h][w] = gout[0] * weight / max(1, n_fg) * (p - y) / max((1 - p) p, 1e-12) on the pixels with label > 0 and exactly 0
+ * on the others; every element is written.  gout: [1] on the DEVICE; stats: what coocc_depth_bce wrote.  One launch. */
+int coocc_depth_bce_bwd(const float* prob, const int32_t* labels, int BN, int D, int h, int w, float weight, const double* stats,
+                        const float* gout, float* dprob, void* stream);
+
 /* ---- DepthNet (co_occ_amd/depth_net.py, csrc/depthnet.hip).  Feature maps are rows [BN*H*W][C], row (b*H + y)*W + x. */
 /* Row table of a 3x3 convolution with dilation = padding = dil on BN maps of H x W: table[3i + j][m] = the row of
  * (y + (i-1) dil, x + (j-1) dil) of the SAME map, or -1 in the padding.  table:[9][BN*H*W], every entry written. */
