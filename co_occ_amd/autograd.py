@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .core import TILE_HINT, conv_desc, launch_conv, lib_pack, out_dim, stream_buffer, workspace, ztrim
+from .core import TILE_HINT, conv_desc, deconv_weight, folded_bn, launch_conv, lib_pack, out_dim, stream_buffer, workspace, ztrim
 
 _F32 = torch.float32
 _tables = {}
@@ -47,6 +47,23 @@ def _amax_word(dev):
 
 def _pad4(n):
     return (n + 3) // 4 * 4
+
+
+def epilogue_bwd(dout, out, scale, relu, pad_to=None, want_res=False, want_bias=False, want_gscale=False):
+    """The backward of a GEMM epilogue y = relu(scale * acc + shift + res) over dout / out [Mo, Cout] (``out`` may be None without
+    ReLU, ``scale`` None for 1) -> (dacc [Mo, pad_to or Cout], zero-filled past Cout; dres [Mo, Cout] | None; dbias [Cout] = the
+    column sums of dacc | None; gscale | None: the device-side {2^k, 2^-k} of max |dacc|, see TRAIN_H2_DGRAD).  The one
+    coocc_conv_epilogue_bwd_ex call; whether the pass is needed at all, and when a gradient scale is wanted, is the caller's."""
+    Mo, Cout = dout.shape
+    dev, Cp = dout.device, pad_to or Cout
+    dacc = torch.zeros(Mo, Cp, device=dev, dtype=_F32) if Cp != Cout else torch.empty(Mo, Cp, device=dev, dtype=_F32)
+    dres = torch.empty(Mo, Cout, device=dev, dtype=_F32) if want_res else None
+    dbias = torch.empty(Cout, device=dev, dtype=_F32) if want_bias else None
+    gscale = torch.empty(2, device=dev, dtype=_F32) if want_gscale else None
+    ws = workspace(dev)
+    call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cp, ptr(dres), Cout,
+         0, ptr(dbias), 0, ptr(ws), ws.numel(), ptr(_amax_word(dev)) if want_gscale else None, ptr(gscale), TRAIN_H2_GRAD_TARGET)
+    return dacc, dres, dbias, gscale
 
 
 def _triple(v):
@@ -346,21 +363,15 @@ class ConvRowsFn(torch.autograd.Function):
         need_x, need_w, need_b, need_res = ctx.needs_input_grad[:4]
         unit, wino3 = strides == _UNIT, _wino_layer(kernel, strides, pads)
         Cp = _pad4(Cout)
-        dacc = torch.zeros(Mo, Cp, device=dev, dtype=_F32) if Cp != Cout else torch.empty(Mo, Cp, device=dev, dtype=_F32)
-        dres = torch.empty(Mo, Cout, device=dev, dtype=_F32) if (has_res and need_res) else None
-        dbias = torch.empty(Cout, device=dev, dtype=_F32) if (has_bias and need_b) else None
         ws = workspace(dev)
         # split-f16 GEMMs that read dacc: max |dacc| collected by the pass that writes dacc -> {scale, 1 / scale} on the device (see
         # TRAIN_H2_DGRAD).  Asked for by the stride-1 dgrad (its K is Cout) and by the layers whose weight gradient has a split-f16
         # form (Winograd domain, one tap); no other layer collects an amax it would never read
-        gscale = None
-        if (core.CONV_ENGINE == "h2" and Cp == Cout and unit and Cin % 4 == 0 and
-                ((TRAIN_H2_DGRAD and need_x and Cout % 32 == 0) or (TRAIN_H2_WGRAD and need_w and (wino3 or taps == 1)))):
-            gscale = torch.empty(2, device=dev, dtype=_F32)
+        want_gscale = (core.CONV_ENGINE == "h2" and Cp == Cout and unit and Cin % 4 == 0 and
+                       ((TRAIN_H2_DGRAD and need_x and Cout % 32 == 0) or (TRAIN_H2_WGRAD and need_w and (wino3 or taps == 1))))
+        dacc, dres, dbias, gscale = epilogue_bwd(dout, out, scale, relu, pad_to=Cp, want_res=has_res and need_res,
+                                                 want_bias=has_bias and need_b, want_gscale=want_gscale)
         gscale_d = gscale if (TRAIN_H2_DGRAD and Cout % 32 == 0) else None      # the dgrad GEMM's K is Cout
-        call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cp,
-             ptr(dres), Cout, 0, ptr(dbias), 0, ptr(ws), ws.numel(), ptr(_amax_word(dev)) if gscale is not None else None,
-             ptr(gscale), TRAIN_H2_GRAD_TARGET)
         if dbias is not None and scale is not None:
             dbias = dbias * scale
         dx = dw = None
@@ -429,14 +440,10 @@ def conv3d_rows(x2d, weight, geom, bias=None, bn=None, stride=1, pad=None, relu=
     """Differentiable Conv3d(+eval BN)(+res)(+ReLU) on rows [B*X*Y*Z, Cin] -> ([B*Xo*Yo*Zo, Cout], out geom).
     ``weight`` [Cout,Cin,kx,ky,kz] (any strides: a permuted view of a reference [.,.,kz,ky,kx] parameter keeps its gradient), or
     [Cout,Cin] for a Linear / 1x1; ``stride`` / ``pad``: an int or a per-axis triple (``pad`` None: k // 2 per axis)."""
-    from .core import fold_bn
     kernel = tuple(weight.shape[2:]) if weight.dim() == 5 else _UNIT
     strides = _triple(stride)
     pads = _triple(pad) if pad is not None else tuple(k // 2 for k in kernel)
-    scale = shift = None
-    if bn is not None:
-        s, b = fold_bn(bn, None)
-        scale, shift = s.to(x2d.device).contiguous(), b.to(x2d.device).contiguous()
+    scale, shift = folded_bn(bn, x2d.device) if bn is not None else (None, None)
     out = ConvRowsFn.apply(x2d.contiguous(), weight, bias, res2d, scale, shift, tuple(geom), kernel, strides, pads, relu)
     return out, (geom[0],) + _out_dims(tuple(geom[1:]), kernel, strides, pads)
 
@@ -790,13 +797,14 @@ def ncdhw_from_rows(rows, geom):
     return rows.view(B, X, Y, Z, rows.shape[1]).permute(0, 4, 1, 2, 3)
 
 
-def conv_bn_rows(x2d, weight, geom, bn=None, bias=None, stride=1, pad=None, relu=True, res2d=None, sync=None):
-    """Conv3d -> BatchNorm (+res) -> ReLU on rows with the norm layer's OWN mode: a BN in training mode normalises with
-    batch (or SyncBN all-reduced, ``sync`` as ``_sync_group`` reads it) statistics and updates its running stats, as
-    nn.BatchNorm3d / nn.SyncBatchNorm do under model.train() upstream; a BN in eval mode is folded into the GEMM epilogue (frozen
-    statistics).  The kernel is ``weight.shape[2:]``; ``stride`` / ``pad`` as ``conv3d_rows`` takes them."""
-    if bn is not None and bn.training:
-        return conv3d_bn_train_rows(x2d, weight, geom, bn, stride=stride, pad=pad, relu=relu, res2d=res2d, bias=bias, sync=sync)
+def conv_bn_rows(x2d, weight, geom, bn=None, bias=None, stride=1, pad=None, relu=True, res2d=None, sync=None, force_train=False):
+    """Conv3d -> BatchNorm (+res) -> ReLU on rows with the norm layer's OWN mode: a BN in training mode (or any BN with
+    ``force_train``) gets the convolution without epilogue and then ``norm_rows`` -- batch (or SyncBN all-reduced) statistics,
+    running stats updated, as nn.BatchNorm3d / nn.SyncBatchNorm do under model.train() upstream; a BN in eval mode is folded into
+    the GEMM epilogue (frozen statistics).  The kernel is ``weight.shape[2:]``; ``stride`` / ``pad`` as ``conv3d_rows`` takes them."""
+    if bn is not None and (bn.training or force_train):
+        y, g = conv3d_rows(x2d, weight, geom, bias=bias, bn=None, stride=stride, pad=pad, relu=False)
+        return norm_rows(y, bn, relu=relu, res=res2d, sync=sync), g
     return conv3d_rows(x2d, weight, geom, bias=bias, bn=bn, stride=stride, pad=pad, relu=relu, res2d=res2d)
 
 
@@ -952,29 +960,31 @@ class FineSampleVoxelFn(torch.autograd.Function):
 
 
 class GroupNormRowsFn(torch.autograd.Function):
-    """nn.GroupNorm on rows [n, C] followed by ReLU (occ_head.py:70-83), differentiable in x, gamma, beta."""
+    """nn.GroupNorm followed by ReLU, differentiable in x, gamma, beta: on rows [n, C], every row its own sample
+    (occ_head.py:70-83), or with ``maps`` = (N, HW) over the N images of [N*HW, C] image rows (occ_head.py:64-68)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, groups, eps, relu):
+    def forward(ctx, x, gamma, beta, groups, eps, relu, maps=None):
         y = x.float().contiguous().clone()
-        n, C = y.shape
-        call("coocc_groupnorm_rows", ptr(y), n, C, C, groups, ptr(gamma.detach().float().contiguous()),
+        # the leading extents of the two entry points: (n, row stride C) | (N, HW)
+        entry, lead = ("coocc_groupnorm_rows", (y.shape[0], y.shape[1])) if maps is None else ("coocc_groupnorm_nhwc", tuple(maps))
+        call(entry, ptr(y), *lead, y.shape[1], groups, ptr(gamma.detach().float().contiguous()),
              ptr(beta.detach().float().contiguous()), float(eps), int(relu))
         ctx.save_for_backward(x.float().contiguous(), y, gamma.detach().float().contiguous())
-        ctx.cfg = (groups, float(eps), int(relu))
+        ctx.cfg = (entry + "_bwd", lead, groups, float(eps), int(relu))
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, gamma = ctx.saved_tensors
-        groups, eps, relu = ctx.cfg
-        n, C = x.shape
+        entry, lead, groups, eps, relu = ctx.cfg
+        C = x.shape[1]
         dx = torch.empty_like(x)
         dgamma = torch.empty(C, device=x.device, dtype=_F32)
         dbeta = torch.empty(C, device=x.device, dtype=_F32)
-        call("coocc_groupnorm_rows_bwd", ptr(x), ptr(y), ptr(dy.float().contiguous()), n, C, C, groups, ptr(gamma), eps, relu,
-             ptr(dx), ptr(dgamma), ptr(dbeta))
-        return dx, dgamma, dbeta, None, None, None
+        call(entry, ptr(x), ptr(y), ptr(dy.float().contiguous()), *lead, C, groups, ptr(gamma), eps, relu, ptr(dx), ptr(dgamma),
+             ptr(dbeta))
+        return dx, dgamma, dbeta, None, None, None, None
 
 
 class FineSampleImgFn(torch.autograd.Function):
@@ -1002,32 +1012,6 @@ class FineSampleImgFn(torch.autograd.Function):
         return dimg, None, None, None, None, None, None
 
 
-class GroupNormNHWCFn(torch.autograd.Function):
-    """nn.GroupNorm over [N, HW, C] image rows followed by ReLU (occ_head.py:64-68)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, N, HW, groups, eps, relu):
-        y = x.float().contiguous().clone()
-        C = y.shape[1]
-        call("coocc_groupnorm_nhwc", ptr(y), N, HW, C, groups, ptr(gamma.detach().float().contiguous()),
-             ptr(beta.detach().float().contiguous()), float(eps), int(relu))
-        ctx.save_for_backward(x.float().contiguous(), y, gamma.detach().float().contiguous())
-        ctx.cfg = (N, HW, groups, float(eps), int(relu))
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, y, gamma = ctx.saved_tensors
-        N, HW, groups, eps, relu = ctx.cfg
-        C = x.shape[1]
-        dx = torch.empty_like(x)
-        dgamma = torch.empty(C, device=x.device, dtype=_F32)
-        dbeta = torch.empty(C, device=x.device, dtype=_F32)
-        call("coocc_groupnorm_nhwc_bwd", ptr(x), ptr(y), ptr(dy.float().contiguous()), N, HW, C, groups, ptr(gamma), eps, relu,
-             ptr(dx), ptr(dgamma), ptr(dbeta))
-        return dx, dgamma, dbeta, None, None, None, None, None
-
-
 def fine_branch_train(head, out_voxel_rows, geom, coarse_lin, img_feats=None, transform=None):
     """Differentiable fine branch (occ_head.py:180-237): the selected coarse voxels' children sample out_voxel_feats
     trilinearly and, with sample_from_img, the image features through the cameras; fine_mlp = Linear -> GroupNorm ->
@@ -1043,7 +1027,7 @@ def fine_branch_train(head, out_voxel_rows, geom, coarse_lin, img_feats=None, tr
         rows = f[0].permute(0, 2, 3, 1).reshape(N_i * Hf * Wf, C_i)            # NHWC rows (a view + copy: plumbing)
         m0 = head.img_mlp_0
         g = linear_rows(rows, m0[0].weight.flatten(1), m0[0].bias, relu=False)
-        g = GroupNormNHWCFn.apply(g, m0[1].weight, m0[1].bias, N_i, Hf * Wf, m0[1].num_groups, m0[1].eps, True)
+        g = GroupNormRowsFn.apply(g, m0[1].weight, m0[1].bias, m0[1].num_groups, m0[1].eps, True, (N_i, Hf * Wf))
 
         class _G:       # geometry holder for the parameter block
             X, Y, Z = geom[1], geom[2], geom[3]
@@ -1139,11 +1123,15 @@ class BatchNormRowsFn(torch.autograd.Function):
         return dx, sums[0], sums[1], dres, None, None, None, None
 
 
-def conv3d_bn_train_rows(x2d, weight, geom, bn, stride=1, pad=None, relu=True, res2d=None, bias=None, sync=None):
-    """Training-mode Conv3d -> BatchNorm (batch statistics) (+res) -> ReLU on rows: the conv runs without epilogue,
-    BatchNormRowsFn normalises.  Use conv3d_rows(bn=...) for frozen statistics."""
-    y, g = conv3d_rows(x2d, weight, geom, bias=bias, bn=None, stride=stride, pad=pad, relu=False)
-    return BatchNormRowsFn.apply(y, bn.weight, bn.bias, res2d, bn, relu, _sync_group(bn, sync)), g
+def norm_rows(y, bn, relu=True, res=None, sync=None, out_h2=None):
+    """``bn`` in training mode on rows (+ res) (+ ReLU): ``BatchNormRowsFn`` with the layer's own parameters and the process group
+    ``_sync_group`` finds for it; ``out_h2`` as the Function takes it."""
+    return BatchNormRowsFn.apply(y, bn.weight, bn.bias, res, bn, relu, _sync_group(bn, sync), out_h2)
+
+
+def conv3d_bn_train_rows(x2d, weight, geom, bn, **kw):
+    """``conv_bn_rows`` with batch statistics whatever the norm layer's mode.  Use conv3d_rows(bn=...) for frozen statistics."""
+    return conv_bn_rows(x2d, weight, geom, bn=bn, force_train=True, **kw)
 
 
 # ----------------------------------------------------------------------------- LiDAR-only trunk (SECOND3D + SECOND3DFPN)
@@ -1190,26 +1178,21 @@ def fpn_sum_rows(ups, strides, C, geom):
 
 
 def deconv_bn_rows(x2d, up, bn, s, relu=True, sync=None):
-    """A SECOND3DFPN deblock -- nn.ConvTranspose3d(kernel = stride = (1,s,s)) -> BN3d -> ReLU (second3d_fpn.py:47-69) -- on the COARSE
-    rows [M, Cin] -> [M, s*s*Cout] (child (kx, ky) of a coarse voxel at columns (kx*s + ky)*Cout ..): the pointwise GEMM with
-    ``core.deconv_weight``'s layout taken as a differentiable view of the parameter (so the weight gradient lands in the module's
-    [Cin,Cout,1,s,s] tensor), then the norm layer in its own mode.  One BN channel serves the s*s children of a coarse voxel, so
-    batch statistics over the [M*s*s, Cout] view of the GEMM's output are those of the upsampled volume; a BN in eval mode is folded
-    into the GEMM's epilogue with its scale / shift repeated s*s times."""
-    cin, cout = up.weight.shape[:2]
-    assert tuple(up.weight.shape[2:]) == (1, s, s), "deconv kernel %s is not (1,%d,%d)" % (tuple(up.weight.shape[2:]), s, s)
-    w = up.weight[:, :, 0].permute(3, 2, 1, 0).reshape(s * s * cout, cin)
+    """A deconvolution deblock with kernel = stride -- nn.ConvTranspose3d((1,s,s)) -> BN3d -> ReLU of SECOND3DFPN
+    (second3d_fpn.py:47-69), or nn.ConvTranspose2d(s) -> BN2d -> ReLU of SECONDFPN (second_fpn.py:44-65) -- on the COARSE rows
+    [M, Cin] -> [M, s*s*Cout] (child (kx, ky) of a coarse voxel, (kh, kw) of a coarse pixel, at columns (kx*s + ky)*Cout ..): the
+    pointwise GEMM with ``core.deconv_weight``'s layout taken as a differentiable view of the parameter (so the weight gradient
+    lands in the module's own tensor), then the norm layer in its own mode.  One BN channel serves the s*s children, so batch
+    statistics over the [M*s*s, Cout] view of the GEMM's output are those of the upsampled volume; a BN in eval mode is folded into
+    the GEMM's epilogue with its scale / shift repeated s*s times."""
+    w = deconv_weight(up.weight, s, detach=False)
+    cout = up.weight.shape[1]
     b = up.bias.repeat(s * s) if up.bias is not None else None
     n = x2d.shape[0]
     if bn is not None and bn.training:
         y = linear_rows(x2d, w, b, relu=False)
-        y = BatchNormRowsFn.apply(y.view(n * s * s, cout), bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync))
-        return y.view(n, s * s * cout)
-    scale = shift = None
-    if bn is not None:
-        from .core import fold_bn
-        sc, sh = fold_bn(bn, None)
-        scale, shift = sc.repeat(s * s).to(x2d.device).contiguous(), sh.repeat(s * s).to(x2d.device).contiguous()
+        return norm_rows(y.view(n * s * s, cout), bn, relu=relu, sync=sync).view(n, s * s * cout)
+    scale, shift = folded_bn(bn, x2d.device, repeat=s * s) if bn is not None else (None, None)
     return ConvRowsFn.apply(x2d.contiguous(), w, b, None, scale, shift, (1, n, 1, 1), _UNIT, _UNIT, _NOPAD, relu)
 
 
@@ -1222,7 +1205,7 @@ class ZyxRowsFn(torch.autograd.Function):
         from .lidar_trunk import bczyx_to_rows
         r = bczyx_to_rows(x.detach())
         ctx.cfg = (r.B, r.X, r.Y, r.Z, r.C)
-        t = r.t if (r.coff == 0 and r.stride == r.C) else r.t[:, r.coff:r.coff + r.C].contiguous()
+        t = r.dense2d()
         return t.clone() if t.data_ptr() == x.data_ptr() else t      # channels-last memory: a view of the input itself
 
     @staticmethod
@@ -1318,10 +1301,7 @@ class StemConvFn(torch.autograd.Function):
         dev = img.device
         dacc = dout.float().contiguous()
         if has_scale or relu:
-            dy, dacc = dacc, torch.empty_like(dacc)
-            ws = workspace(dev)
-            call("coocc_conv_epilogue_bwd_ex", ptr(dy), C0, ptr(out), C0, ptr(scale) if has_scale else None, out.shape[0], C0, int(relu),
-                 ptr(dacc), C0, None, C0, 0, None, 0, ptr(ws), ws.numel(), None, None, TRAIN_H2_GRAD_TARGET)
+            dacc = epilogue_bwd(dacc, out, scale if has_scale else None, relu)[0]
         dw = torch.empty(147, C0, device=dev, dtype=_F32)
         nb = int(_lib.load().coocc_img_stem_wgrad_ws(BN, H, W))
         part = stream_buffer(dev, "s:stem_wgrad", (nb + 3) // 4)
@@ -1333,14 +1313,11 @@ class StemConvFn(torch.autograd.Function):
 def stem_conv_bn_rows(img, conv, bn, relu=True, sync=None):
     """The ResNet stem's Conv2d(3, 64, 7, 2, 3) -> BN -> ReLU on rows with the norm layer's own mode (as ``conv_bn_rows``) ->
     (rows [BN*Hc*Wc, 64], (BN, Hc, Wc, 1))."""
-    from .core import fold_bn
     BN, _, H, W = img.shape
     geom = (BN, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 1)
     if bn.training:
-        y = StemConvFn.apply(img, conv.weight, None, None, False)
-        return BatchNormRowsFn.apply(y, bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync)), geom
-    s, b = fold_bn(bn, conv.bias)
-    return StemConvFn.apply(img, conv.weight, s.to(img.device).contiguous(), b.to(img.device).contiguous(), relu), geom
+        return norm_rows(StemConvFn.apply(img, conv.weight, None, None, False), bn, relu=relu, sync=sync), geom
+    return StemConvFn.apply(img, conv.weight, *folded_bn(bn, img.device, conv.bias), relu), geom
 
 
 class MaxPoolRowsFn(torch.autograd.Function):
@@ -1377,25 +1354,3 @@ def maxpool_rows(x2d, geom):
     """-> (pooled rows, (BN, Hp, Wp, 1)) of rows with geom (BN, Hc, Wc, 1)."""
     BN, Hc, Wc = geom[:3]
     return MaxPoolRowsFn.apply(x2d, (BN, Hc, Wc)), (BN, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1, 1)
-
-
-def deconv2d_bn_rows(x2d, up, bn, s, relu=True, sync=None):
-    """``deconv_bn_rows`` for a 2-D deblock -- nn.ConvTranspose2d(kernel = stride = s) -> BN2d -> ReLU (second_fpn.py:44-65) -- on
-    the COARSE rows [M, Cin] -> [M, s*s*Cout], child (kh, kw) of a coarse pixel at columns (kh*s + kw)*Cout ..: the weight
-    [Cin,Cout,s,s] is taken as a differentiable view in ``image_encoder.deconv2d_weight``'s layout, so its gradient lands in the
-    module's parameter; batch statistics over the [M*s*s, Cout] view are those of the upsampled map."""
-    cin, cout = up.weight.shape[:2]
-    assert tuple(up.weight.shape[2:]) == (s, s), "deconv kernel %s is not (%d,%d)" % (tuple(up.weight.shape[2:]), s, s)
-    w = up.weight.permute(2, 3, 1, 0).reshape(s * s * cout, cin)
-    b = up.bias.repeat(s * s) if up.bias is not None else None
-    n = x2d.shape[0]
-    if bn is not None and bn.training:
-        y = linear_rows(x2d, w, b, relu=False)
-        y = BatchNormRowsFn.apply(y.view(n * s * s, cout), bn.weight, bn.bias, None, bn, relu, _sync_group(bn, sync))
-        return y.view(n, s * s * cout)
-    scale = shift = None
-    if bn is not None:
-        from .core import fold_bn
-        sc, sh = fold_bn(bn, None)
-        scale, shift = sc.repeat(s * s).to(x2d.device).contiguous(), sh.repeat(s * s).to(x2d.device).contiguous()
-    return ConvRowsFn.apply(x2d.contiguous(), w, b, None, scale, shift, (1, n, 1, 1), _UNIT, _UNIT, _NOPAD, relu)

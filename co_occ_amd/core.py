@@ -183,6 +183,10 @@ class Rows:
             v._coocc_rows = (self, v._version)
         return v
 
+    def dense2d(self):
+        """The rows as a dense [B*V, C] tensor: ``t`` itself when the C channels are all of it, else a copy of their columns."""
+        return self.t if (self.coff == 0 and self.stride == self.C) else self.t[:, self.coff:self.coff + self.C].contiguous()
+
 
 def to_rows(x):
     """[B,C,X,Y,Z] tensor (any strides) -> Rows, converting with the HIP transpose if needed."""
@@ -232,18 +236,34 @@ def fold_bn(bn, conv_bias=None):
     return scale.float(), bias.float()
 
 
+def folded_bn(bn, dev, conv_bias=None, repeat=1):
+    """``fold_bn`` as a GEMM epilogue reads it: (scale, shift) on ``dev``, contiguous, each repeated ``repeat`` times (one BN channel
+    serving the s*s children of a deconvolution)."""
+    return tuple((v.repeat(repeat) if repeat != 1 else v).to(dev).contiguous() for v in fold_bn(bn, conv_bias))
+
+
 def zyx_weight(w):
     """A conv weight of the reference's [B,C,Z,Y,X] modules, [N,C,kD,kH,kW] = [N,C,kz,ky,kx], in this package's axis order
     [N,C,kx,ky,kz] (tap t = (dx*ky + dy)*kz + dz after flattening)."""
     return w.detach().permute(0, 1, 4, 3, 2).contiguous()
 
 
-def deconv_weight(w, s):
-    """nn.ConvTranspose3d(kernel = stride = (1,s,s)) weight [Cin,Cout,1,s,s] ((kz,ky,kx) order) as the pointwise GEMM that produces
-    every coarse voxel's s*s children: [s*s*Cout, Cin], row (kx*s + ky)*Cout + co  (out[x*s + kx, y*s + ky] = W[:, co, 0, ky, kx] . in[x, y])."""
+def deconv_weight(w, s, detach=True):
+    """A deconvolution with kernel = stride as the pointwise GEMM that produces every coarse voxel's s*s children, [s*s*Cout, Cin]:
+    nn.ConvTranspose3d(kernel (1,s,s)) weight [Cin,Cout,1,s,s] ((kz,ky,kx) order), row (kx*s + ky)*Cout + co  (out[x*s + kx, y*s + ky]
+    = W[:, co, 0, ky, kx] . in[x, y]); nn.ConvTranspose2d weight [Cin,Cout,s,s], row (kh*s + kw)*Cout + co  (out[h*s + kh, w*s + kw] =
+    W[:, co, kh, kw] . in[h, w]; X = H, Y = W).  ``detach=False``: the differentiable view of the parameter, not made contiguous."""
     cin, cout = w.shape[:2]
-    assert tuple(w.shape[2:]) == (1, s, s), "deconv kernel %s is not (1,%d,%d)" % (tuple(w.shape[2:]), s, s)
-    return w.detach()[:, :, 0].permute(3, 2, 1, 0).reshape(s * s * cout, cin).contiguous()
+    if detach:
+        w = w.detach()
+    if w.dim() == 5:
+        assert tuple(w.shape[2:]) == (1, s, s), "deconv kernel %s is not (1,%d,%d)" % (tuple(w.shape[2:]), s, s)
+        v = w[:, :, 0].permute(3, 2, 1, 0)
+    else:
+        assert tuple(w.shape[2:]) == (s, s), "deconv kernel %s is not (%d,%d)" % (tuple(w.shape[2:]), s, s)
+        v = w.permute(2, 3, 1, 0)
+    v = v.reshape(s * s * cout, cin)
+    return v.contiguous() if detach else v
 
 
 def lib_pack(entry, w, *dims):
@@ -310,8 +330,7 @@ class PackedConv:
         dev = weight.device
         self.w = lib_pack("coocc_conv_pack_weights", w, self.Cout, self.Cin, taps, int(tap_major)).to(dev)
         if bn is not None:
-            s, b = fold_bn(bn, bias)
-            self.scale, self.bias = s.to(dev).contiguous(), b.to(dev).contiguous()
+            self.scale, self.bias = folded_bn(bn, dev, bias)
         else:
             self.scale = None
             self.bias = bias.detach().float().to(dev).contiguous() if bias is not None else None

@@ -497,20 +497,13 @@ def dropout_rows(x2d, p, generator=None):
     return DropoutRowsFn.apply(x2d, mask, p)
 
 
-def bn_rows(y, bn, relu=False, res=None):
-    """A BatchNorm in training mode on rows (batch statistics, running statistics updated): ``autograd.BatchNormRowsFn``."""
-    ag = _ag()
-    return ag.BatchNormRowsFn.apply(y, bn.weight, bn.bias, res, bn, relu, ag._sync_group(bn, None))
-
-
 def conv3x3_train(x2d, geom, weight, bn=None, bias=None, relu=True, res=None):
     """Conv2d 3x3 padding 1 (-> batch-statistics BN (+ res)) (-> ReLU) on rows through ``autograd.conv_bn_rows`` with kernel (3, 3, 1)."""
     ag = _ag()
     w5 = weight.unsqueeze(-1)
     if bn is None or res is None:
         return ag.conv_bn_rows(x2d, w5, geom, bn=bn, bias=bias, relu=relu)[0]
-    y = ag.conv_bn_rows(x2d, w5, geom, bn=None, bias=bias, relu=False)[0]
-    return bn_rows(y, bn, relu=relu, res=res)
+    return ag.norm_rows(ag.conv_bn_rows(x2d, w5, geom, bn=None, bias=bias, relu=False)[0], bn, relu=relu, res=res)
 
 
 def bias_rows(y, bias, geom):
@@ -688,18 +681,18 @@ class DepthNet(nn.Module):
         aspp = self.depth_conv[3]
         BN, H, W = geom
         mid, dev = self.mid_channels, h.device
-        outs = [bn_rows(ag.linear_rows(h, aspp.aspp1.atrous_conv.weight.reshape(mid, mid)), aspp.aspp1.bn, relu=True)]
+        outs = [ag.norm_rows(ag.linear_rows(h, aspp.aspp1.atrous_conv.weight.reshape(mid, mid)), aspp.aspp1.bn, relu=True)]
         tables, taps = self._aspp_tables(BN, H, W, dev)
         for m, tb, tp in zip((aspp.aspp2, aspp.aspp3, aspp.aspp4), tables, taps):
-            outs.append(bn_rows(dilated_train(h, m.atrous_conv.weight, tb, tp), m.bn, relu=True))
+            outs.append(ag.norm_rows(dilated_train(h, m.atrous_conv.weight, tb, tp), m.bn, relu=True))
         w1 = aspp.conv1.weight.reshape(mid, 5 * mid)
         y = ag.linear_rows(torch.cat(outs, 1), w1[:, :4 * mid].contiguous())
         # the pooled branch is constant over a camera's map: its slice of the 1x1 is one vector per camera, added UN-NORMALISED to the
         # four real slices' sum (bn1's batch statistics are those of the whole sum, so nothing can be folded as in eval)
-        g = bn_rows(ag.linear_rows(CamMeanFn.apply(h, BN, H * W), aspp.global_avg_pool[1].weight.reshape(mid, mid)),
-                    aspp.global_avg_pool[2], relu=True)
+        g = ag.norm_rows(ag.linear_rows(CamMeanFn.apply(h, BN, H * W), aspp.global_avg_pool[1].weight.reshape(mid, mid)),
+                         aspp.global_avg_pool[2], relu=True)
         y = CamAddFn.apply(y, ag.linear_rows(g, w1[:, 4 * mid:].contiguous()), BN, H * W)
-        y = bn_rows(y, aspp.bn1, relu=True)
+        y = ag.norm_rows(y, aspp.bn1, relu=True)
         return dropout_rows(y, float(aspp.dropout.p), self.dropout_generator)
 
     def forward_rows_train(self, x2d, geom, mlp_input):

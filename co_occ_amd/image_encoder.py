@@ -38,7 +38,7 @@ from torch import nn
 
 from . import _lib, core
 from ._lib import call, ptr
-from .core import PackCache, PackedConv, Rows, conv_rows, fold_bn
+from .core import PackCache, PackedConv, Rows, conv_rows
 from .depth_net import conv3x3_pack
 from .registry import Registry
 
@@ -148,8 +148,7 @@ def _bn2d(norm_cfg, n, what):
 def stem_pack(conv1, bn1):
     """(w [147, 64] with row (ci*7 + ky)*7 + kx, scale [64], bias [64]) of csrc/img_stem.hip on the weight's device."""
     w = conv1.weight.detach().float()
-    scale, bias = fold_bn(bn1, conv1.bias)
-    return (w.permute(1, 2, 3, 0).reshape(-1, w.shape[0]).contiguous(), scale.to(w.device).contiguous(), bias.to(w.device).contiguous())
+    return (w.permute(1, 2, 3, 0).reshape(-1, w.shape[0]).contiguous(),) + core.folded_bn(bn1, w.device, conv1.bias)
 
 
 def stem_rows(img, pack, relu=True, pool=True, twin_for=()):
@@ -423,14 +422,6 @@ class ResNet(nn.Module):
         return tuple(rows_as_bchw(r) for r in self.forward_rows(x))
 
 
-def deconv2d_weight(w, s):
-    """nn.ConvTranspose2d(kernel = stride = s) weight [Cin,Cout,s,s] as the pointwise GEMM that produces every coarse pixel's s*s
-    children: [s*s*Cout, Cin], row (kh*s + kw)*Cout + co  (out[h*s + kh, w*s + kw] = W[:, co, kh, kw] . in[h, w]; X = H, Y = W)."""
-    cin, cout = w.shape[:2]
-    assert tuple(w.shape[2:]) == (s, s), "deconv kernel %s is not (%d,%d)" % (tuple(w.shape[2:]), s, s)
-    return w.detach().permute(2, 3, 1, 0).reshape(s * s * cout, cin).contiguous()
-
-
 @IMAGE_NECKS.register_module()
 class SECONDFPN(nn.Module):
     def __init__(self, in_channels=[128, 128, 256], out_channels=[256, 256, 256], upsample_strides=[1, 2, 4],
@@ -494,7 +485,7 @@ class SECONDFPN(nn.Module):
             return ag.conv_bn_rows(x2d, w, geom, bn=bn, bias=up.bias, stride=(k, k, 1), pad=0, relu=True)
         if k == 1:
             return ag.conv_bn_rows(x2d, up.weight[:, :, 0, 0].t(), geom, bn=bn, bias=up.bias, relu=True)
-        y = ag.deconv2d_bn_rows(x2d, up, bn, k, relu=True)
+        y = ag.deconv_bn_rows(x2d, up, bn, k, relu=True)
         fine = (B, H * k, W * k, 1)
         return ag.fpn_sum_rows([y], [k], oc, fine), fine
 
@@ -517,10 +508,9 @@ class SECONDFPN(nn.Module):
             for (kind, k), blk in zip(self.levels, self.deblocks):
                 up, bn = blk[0], blk[1]
                 if kind == "deconv":
-                    pc = PackedConv(deconv2d_weight(up.weight, k), ksize=1)
-                    sc, bi = fold_bn(bn, up.bias)                      # one BN channel serves the k*k children of a coarse pixel
-                    dev = up.weight.device
-                    pc.scale, pc.bias = sc.repeat(k * k).to(dev).contiguous(), bi.repeat(k * k).to(dev).contiguous()
+                    pc = PackedConv(core.deconv_weight(up.weight, k), ksize=1)
+                    # one BN channel serves the k*k children of a coarse pixel
+                    pc.scale, pc.bias = core.folded_bn(bn, up.weight.device, up.bias, repeat=k * k)
                 elif k == 1:
                     pc = PackedConv(up.weight.detach().reshape(up.weight.shape[0], -1), bn=bn, bias=up.bias, ksize=1)
                 else:

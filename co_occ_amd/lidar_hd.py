@@ -328,12 +328,7 @@ class SparseConvV1Fn(torch.autograd.Function):
         dacc, gscale, dres = dout, None, None
         if Mo and (h2g or relu or scale is not None or need_res):
             # the epilogue's backward (ReLU mask, folded scale, residual) and, for the split-f16 dgrad / wgrad, max |dacc| -> {2^k, 2^-k}
-            dacc = torch.empty(Mo, Cout, device=dev, dtype=_F32)
-            dres = torch.empty(Mo, Cout, device=dev, dtype=_F32) if need_res else None
-            gscale = torch.empty(2, device=dev, dtype=_F32) if h2g else None
-            ws = core.workspace(dev)
-            call("coocc_conv_epilogue_bwd_ex", ptr(dout), Cout, ptr(out), Cout, ptr(scale), Mo, Cout, int(relu), ptr(dacc), Cout, ptr(dres),
-                 Cout, 0, None, 0, ptr(ws), ws.numel(), ptr(ag._amax_word(dev)) if h2g else None, ptr(gscale), ag.TRAIN_H2_GRAD_TARGET)
+            dacc, dres, _, gscale = ag.epilogue_bwd(dout, out, scale, relu, want_res=need_res, want_gscale=h2g)
         elif need_res:
             dres = dout
         dx = dw = None
@@ -370,18 +365,16 @@ class SparseConvV1Fn(torch.autograd.Function):
 def conv_bn_train(f, fh, conv, bn, table, bwd, res=None, twin=True):
     """SparseConvV1 -> BN1d (+ res) -> ReLU on rows, differentiable: (rows, their split-f16 twin or None).  ``f`` [n_in, pad4(Cin)]
     with its twin ``fh`` (or None), ``table`` / ``bwd`` the forward and transposed books (``SparseConvV1Fn``).  The norm follows its
-    own ``training`` flag: batch statistics (``autograd.BatchNormRowsFn``, whose apply pass writes the twin when the split-f16
+    own ``training`` flag: batch statistics (``autograd.norm_rows``, whose apply pass writes the twin when the split-f16
     engine will read it), or its folded running statistics in the GEMM's epilogue."""
     from . import autograd as ag
     if not bn.training:
-        s, b = fold_bn(bn)
-        dev = f.device
-        return SparseConvV1Fn.apply(f, conv.weight, table, bwd, fh, s.to(dev).contiguous(), b.to(dev).contiguous(), res, True), None
+        return SparseConvV1Fn.apply(f, conv.weight, table, bwd, fh, *core.folded_bn(bn, f.device), res, True), None
     y = SparseConvV1Fn.apply(f, conv.weight, table, bwd, fh, None, None, None, False)
     if y.shape[0] == 0:                     # no active row: nothing to normalise, no statistic to update; zero gradients
         return y + (bn.weight.sum() + bn.bias.sum()) * 0, None
     yh = torch.empty_like(y) if (twin and _train_h2() and y.shape[1] % 32 == 0) else None
-    return ag.BatchNormRowsFn.apply(y, bn.weight, bn.bias, res, bn, True, ag._sync_group(bn, None), yh), yh
+    return ag.norm_rows(y, bn, res=res, out_h2=yh), yh
 
 
 @MIDDLE_ENCODERS_HD.register_module()

@@ -18,7 +18,7 @@ from torch import nn
 
 from . import _lib, core
 from .backbone import build_bn
-from .core import PackCache, PackedConv, Rows, conv_rows, fold_bn
+from .core import PackCache, PackedConv, Rows, conv_rows
 from ._lib import call, ptr
 from .registry import BACKBONES, NECKS
 
@@ -272,9 +272,8 @@ class SECOND3DFPN(nn.Module):
                 up, bn = blk[0], blk[1]
                 if isinstance(up, nn.ConvTranspose3d):
                     pc = PackedConv(core.deconv_weight(up.weight, s), ksize=1)
-                    sc, bi = fold_bn(bn, up.bias)                     # one BN channel serves the s*s children of a coarse voxel
-                    dev = up.weight.device
-                    pc.scale, pc.bias = sc.repeat(s * s).to(dev).contiguous(), bi.repeat(s * s).to(dev).contiguous()
+                    # one BN channel serves the s*s children of a coarse voxel
+                    pc.scale, pc.bias = core.folded_bn(bn, up.weight.device, up.bias, repeat=s * s)
                 else:
                     pc = PackedConv(up.weight, bn=bn, bias=up.bias, ksize=1)
                 de.append(pc)
@@ -329,9 +328,7 @@ def run_trunk_train(backbone, neck, x):
     parameters and state_dict keys are shared, and ``run_trunk`` re-packs from the stepped parameters afterwards (``PackCache``)."""
     from . import autograd as ag
     if isinstance(x, Rows):
-        r = x
-        x2d = r.t if (r.coff == 0 and r.stride == r.C) else r.t[:, r.coff:r.coff + r.C].contiguous()
-        geom = (r.B, r.X, r.Y, r.Z)
+        x2d, geom = x.dense2d(), (x.B, x.X, x.Y, x.Z)
     else:
         if not torch.is_tensor(x) or x.dim() != 5:
             raise ValueError("expected a [B,C,Z,Y,X] tensor")
@@ -342,8 +339,7 @@ def run_trunk_train(backbone, neck, x):
         if x.requires_grad:
             x2d = ag.ZyxRowsFn.apply(x)
         else:
-            r = bczyx_to_rows(x)
-            x2d = r.t if (r.coff == 0 and r.stride == r.C) else r.t[:, r.coff:r.coff + r.C].contiguous()
+            x2d = bczyx_to_rows(x).dense2d()
     feats = ag.second3d_forward_train(backbone, x2d, geom)
     out, g = ag.second3dfpn_forward_train(neck, feats)
     return Rows(out, g[0], g[1], g[2], g[3], out.shape[1])

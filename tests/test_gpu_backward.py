@@ -410,6 +410,31 @@ def test_groupnorm_rows_backward(dev):
     assert_close(bd.grad.cpu(), gn.bias.grad, what="gn dbeta")
 
 
+def test_groupnorm_maps_backward(dev):
+    """``maps`` = (N, HW): the statistics are those of an image's HW rows, as torch GroupNorm on [N,C,HW].  Two images, an HW (15)
+    that no tile of the kernel divides."""
+    g = torch.Generator().manual_seed(18)
+    N, HW, C, groups = 2, 15, 64, 16
+    x = torch.randn(N * HW, C, generator=g)
+    gn = torch.nn.GroupNorm(groups, C)
+    gn.weight.data.copy_(torch.rand(C, generator=g) + 0.5)
+    gn.bias.data.copy_(torch.randn(C, generator=g) * 0.2)
+    gout = torch.randn(N * HW, C, generator=g)
+
+    def torch_gn(rows):         # rows [N*HW, C] -> GroupNorm + ReLU on [N,C,HW] -> rows
+        return F.relu(gn(rows.view(N, HW, C).permute(0, 2, 1))).permute(0, 2, 1).reshape(N * HW, C)
+    xr = x.clone().requires_grad_()
+    torch_gn(xr).backward(gout)
+    xd = x.to(dev).requires_grad_()
+    wd, bd = gn.weight.detach().clone().to(dev).requires_grad_(), gn.bias.detach().clone().to(dev).requires_grad_()
+    y = ag.GroupNormRowsFn.apply(xd, wd, bd, groups, gn.eps, True, (N, HW))
+    assert_close(y.detach().cpu(), torch_gn(x).detach(), what="gn maps forward")
+    y.backward(gout.to(dev))
+    assert_close(xd.grad.cpu(), xr.grad, what="gn maps dx")
+    assert_close(wd.grad.cpu(), gn.weight.grad, what="gn maps dgamma")
+    assert_close(bd.grad.cpu(), gn.bias.grad, what="gn maps dbeta")
+
+
 def test_fine_branch_backward_vs_torch(dev):
     """Voxel-only fine branch: trilinear grid_sample adjoint (atomics) + Linear + GroupNorm + ReLU + Linear against torch
     autograd of F.grid_sample (align_corners=False, zeros) with the reference's coordinate normalisation."""

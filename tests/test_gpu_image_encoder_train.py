@@ -9,14 +9,17 @@ Whole modules: outputs and running statistics against that judge; parameter grad
 derivative taken at the device's own sign pattern (``judge_forward`` says why).  Measured on the MI355X (ratio = error / the
 anchor's own error, budget 4 max / 2 rms), worst over frozen_stages -1 / 0 / 2: gradients 1.75 / 1.25, running statistics
 1.83 / 1.08, outputs 1.17 / 1.02 -- no tensor needed the ``LOOSE`` fallback below."""
+import copy
 import ctypes
 
 import pytest
 import torch
 import torch.nn.functional as F
+from torch import nn
 
 import co_occ_amd as pkg
 import ref_image_encoder as R
+import util
 from co_occ_amd import autograd as ag, core, image_encoder as IE, synth
 from co_occ_amd._lib import call, ptr
 from util import assert_close, assert_precise, precision
@@ -492,6 +495,61 @@ def test_neck_alone_with_both_deblock_kinds(dev):
                 assert int(b) == 1
             else:
                 assert_precise(b.cpu(), r64["stats"][k], r32["stats"][k], what=what + "stat " + k)
+    core.check_h2_overflow()
+
+
+def _cmp(got, r64, r32, what, tol=util.TOL):
+    """``util.TOL`` scale-relative, under the condition that the fp32 torch evaluation is within a quarter of it (the rule of the
+    3-D deblock test in test_gpu_trunk_train.py)."""
+    e32 = util.rel_err(r32, r64)
+    assert e32 <= tol / 4, "%s: the fp32 torch evaluation is %.3e from float64: TOL does not judge this fixture" % (what, e32)
+    e = util.rel_err(got, r64)
+    print("[image-encoder-train] %-40s scale-relative %.3e (fp32 torch %.3e)" % (what, e, e32))
+    assert e <= tol, "%s: %.3e from float64" % (what, e)
+
+
+@pytest.mark.parametrize("s,train", [(2, True), (4, True), (2, False)])
+def test_deblock_2d_through_deconv_bn_rows_against_float64(dev, s, train):
+    """ConvTranspose2d(kernel = stride = s) + BatchNorm2d + ReLU through ``autograd.deconv_bn_rows``, the mirror of the 3-D deblock
+    test in test_gpu_trunk_train.py: output, dx, dW (and, with batch statistics, dgamma, dbeta) within ``util.TOL`` (scale-relative)
+    of float64 torch, where the fp32 torch evaluation is within TOL / 4.  Running statistics under train(): torch's update (momentum
+    0.1, unbiased variance) to 1e-5, as derived there for these counts (n = 96 and 384 values per channel); in eval mode (the BN
+    folded into the GEMM's epilogue) they are untouched."""
+    Cin, Cout, (BN, H, W) = 32, 16, (2, 3, 4)
+    gen = torch.Generator().manual_seed(60 + s)
+    blk = nn.Sequential(nn.ConvTranspose2d(Cin, Cout, s, stride=s, bias=False), nn.BatchNorm2d(Cout, eps=1e-3, momentum=0.1), nn.ReLU())
+    blk.load_state_dict(synth.random_state_dict(blk.state_dict(), seed=60 + s))
+    x = torch.randn(BN, Cin, H, W, generator=gen)
+    up = torch.randn(BN, Cout, H * s, W * s, generator=gen)
+    refs = {}
+    for dt in (torch.float64, torch.float32):
+        m = copy.deepcopy(blk).to(dt).train(train)
+        xa = x.to(dt, copy=True).requires_grad_()       # a copy: x.to(float32) is x itself, and x stays a plain input
+        y = m(xa)
+        y.backward(up.to(dt))
+        refs[dt] = dict(y=y.detach(), dx=xa.grad, dw=m[0].weight.grad, dg=m[1].weight.grad, db=m[1].bias.grad, rm=m[1].running_mean,
+                        rv=m[1].running_var, nb=int(m[1].num_batches_tracked))
+    m = copy.deepcopy(blk).to(dev).train(train)
+    xd = x.to(dev).requires_grad_()
+    u = ag.deconv_bn_rows(rows_of(xd), m[0], m[1], s)
+    out = ag.fpn_sum_rows([u], [s], Cout, (BN, H * s, W * s, 1))
+    out.backward(rows_of(up).to(dev))
+    got = dict(y=as_bchw(out.detach(), BN, H * s, W * s), dx=xd.grad, dw=m[0].weight.grad)
+    if train:
+        got.update(dg=m[1].weight.grad, db=m[1].bias.grad)
+    else:
+        assert m[1].weight.grad is None and m[1].bias.grad is None          # folded: constants of the epilogue
+    assert tuple(m[0].weight.grad.shape) == (Cin, Cout, s, s)
+    for k, v in got.items():
+        _cmp(v.cpu(), refs[torch.float64][k], refs[torch.float32][k], "deblock 2d s%d train=%d %s" % (s, train, k))
+    r = refs[torch.float64]
+    assert int(m[1].num_batches_tracked) == r["nb"] == int(train)
+    for k, v in (("rm", m[1].running_mean), ("rv", m[1].running_var)):
+        if train:
+            e = util.rel_err(v.cpu(), r[k])
+            assert e <= 1e-5, "running statistic %s: %.3e" % (k, e)
+        else:
+            assert torch.equal(v.cpu(), blk[1].state_dict()["running_mean" if k == "rm" else "running_var"]), k
     core.check_h2_overflow()
 
 

@@ -67,6 +67,36 @@ def test_fold_bn_matches_batchnorm_eval():
     s, b = core.fold_bn(bn)
     x = torch.randn(2, 7, 3, 3, 3, generator=g)
     assert torch.allclose(bn(x), x * s.view(1, 7, 1, 1, 1) + b.view(1, 7, 1, 1, 1), atol=1e-6)
+    s3, b3 = core.folded_bn(bn, torch.device("cpu"), repeat=3)
+    assert torch.equal(s3, s.repeat(3)) and torch.equal(b3, b.repeat(3)) and s3.is_contiguous() and b3.is_contiguous()
+    cb = torch.randn(7, generator=g)
+    assert all(torch.equal(u, v) for u, v in zip(core.folded_bn(bn, torch.device("cpu"), cb), core.fold_bn(bn, cb)))
+
+
+@pytest.mark.parametrize("s", [2, 4])
+@pytest.mark.parametrize("rank", [3, 2])
+def test_deconv_weight_of_both_ranks_is_the_two_former_expressions(rank, s):
+    """``core.deconv_weight`` against the expression each rank had of its own ([Cin,Cout,1,s,s]: the 3-D deblock's, [Cin,Cout,s,s]:
+    the 2-D one's), value for value; detached and contiguous by default, and with ``detach=False`` attached to the parameter, whose
+    gradient is then that of the former expression."""
+    cin, cout = 5, 3
+    g = torch.Generator().manual_seed(10 * rank + s)
+    w = torch.nn.Parameter(torch.randn(*((cin, cout, 1, s, s) if rank == 3 else (cin, cout, s, s)), generator=g))
+
+    def former(p):
+        v = p[:, :, 0].permute(3, 2, 1, 0) if rank == 3 else p.permute(2, 3, 1, 0)
+        return v.reshape(s * s * cout, cin)
+    d = core.deconv_weight(w, s)
+    assert torch.equal(d, former(w.detach())) and d.is_contiguous() and not d.requires_grad
+    v = core.deconv_weight(w, s, detach=False)
+    assert v.requires_grad and torch.equal(v.detach(), former(w.detach()))
+    r = torch.randn(s * s * cout, cin, generator=g)
+    (v * r).sum().backward()
+    w2 = w.detach().clone().requires_grad_()
+    (former(w2) * r).sum().backward()
+    assert w.grad is not None and tuple(w.grad.shape) == tuple(w.shape) and torch.equal(w.grad, w2.grad)
+    with pytest.raises(AssertionError, match="deconv kernel"):
+        core.deconv_weight(w, s + 1)
 
 
 def test_cpu_tensors_are_refused_not_emulated():
