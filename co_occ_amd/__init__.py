@@ -30,6 +30,7 @@ from .lidar_hd import SparseEncoderHD
 from . import depth_net
 from .depth_net import DepthNet
 from .evaluation import SemanticEvaluator, cm_to_ious, evaluation_semantic
+from . import optim
 
 register_into_mmdet()
 

@@ -211,6 +211,11 @@ SIGNATURES = {
     "coocc_maxpool2d_rows_bwd": (I, [P, I, P, I, I, I, I, I, P, I, P]),
     "coocc_img_stem_wgrad_ws": (Z, [I, I, I]),
     "coocc_img_stem_wgrad": (I, [P, I, I, I, P, I, I, P, P, Z, P]),
+    "coocc_optim_chunk": (I, []),
+    "coocc_optim_sumsq": (I, [P, P, I, P, I, P, P]),
+    "coocc_optim_clip_coef": (I, [P, I, F, P, P, P, P]),
+    "coocc_optim_adamw": (I, [P, P, I, P, I, P, I, P]),
+    "coocc_optim_scale": (I, [P, P, I, P, I, P, P]),
 }
 
 _lib = None

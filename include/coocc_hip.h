@@ -1029,6 +1029,49 @@ size_t coocc_img_stem_wgrad_ws(int BN, int H, int W);
 int coocc_img_stem_wgrad(const float* img, int BN, int H, int W, const float* dy, int dy_stride, int C0, float* dw, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* ---- the parameter update: AdamW with gradient-norm clipping (co_occ_amd/optim.py, csrc/optim.hip).  Work is
+ * described by two tables the host fills each step.  The tensor table has one coocc_optim_tensor per parameter that has a
+ * gradient.  The chunk table has one (tensor index, element offset) pair of int64 per chunk: every tensor is cut into chunks of
+ * coocc_optim_chunk() elements (the last one shorter), tensors in table order, offsets ascending.  Every entry takes the tensor
+ * table twice: `tensors` on the device (what the kernels read) and `tensors_host`, the same bytes in host memory, which the entry
+ * reads before it launches to check every numel and pointer and that `nchunks` is the tables' own chunk count.  No entry reads
+ * device memory on the host, allocates or synchronises. */
+typedef struct coocc_optim_tensor {
+  float* p;                /* parameter, fp32, contiguous, 4-byte aligned (16-byte aligned: the vector path) */
+  float* g;                /* its gradient (written only by coocc_optim_scale and coocc_optim_adamw with write_grad) */
+  float* exp_avg;          /* first moment  (coocc_optim_adamw only; NULL elsewhere) */
+  float* exp_avg_sq;       /* second moment (coocc_optim_adamw only; NULL elsewhere) */
+  int64_t numel;           /* > 0 */
+  double lr, weight_decay, beta1, beta2, eps;
+  double bias_correction1; /* 1 - beta1^t, t = this parameter's own step count after the increment, in float64 on the host */
+  double bias_correction2; /* 1 - beta2^t */
+} coocc_optim_tensor;
+/* Elements per chunk: a compile-time constant of the library and part of the determinism contract (the partial sums of the norm
+ * are per chunk). */
+int coocc_optim_chunk(void);
+/* partials[c] = the sum of g^2 over chunk c in float64 (the square of an fp32 value is exact there), in an order that depends on
+ * the chunk's length alone: thread t of 256 adds the elements of its groups of four t, t + 256, ... in index order, the wave adds
+ * its lanes in a fixed butterfly, lane 0 adds the four waves in wave order.  The pointer's alignment selects 16-byte or 4-byte
+ * loads and never the order.  One workgroup per chunk. */
+int coocc_optim_sumsq(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
+                      int nchunks, double* partials, void* stream);
+/* norm64[0] = sqrt(partials[0] + ... in a fixed order), norm32[0] = (float)norm64[0], coef[0] = min(1, max_norm / (norm32 + 1e-6))
+ * in fp32 -- torch.nn.utils.clip_grad_norm_'s expression; a non-finite norm propagates into coef (error_if_nonfinite=False).
+ * One workgroup. */
+int coocc_optim_clip_coef(const double* partials, int nchunks, float max_norm, double* norm64, float* norm32, float* coef,
+                          void* stream);
+/* torch's non-amsgrad AdamW step on every element of every tensor, in torch's operation order: g' = g * coef[0] (coef == NULL:
+ * g' = g),  p *= 1 - lr wd;  m += (g' - m)(1 - beta1);  v = v beta2 + g' g' (1 - beta2);  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2)
+ * + eps).  p, g, m, v are fp32 in memory; one element's chain runs in fp64 registers with the table's float64 scalars and rounds once
+ * per stored value.  write_grad != 0: g' (the fp32 product g * coef) is stored back into g.
+ * 16-byte loads and stores where all four pointers of a tensor are 16-byte aligned, 4-byte ones otherwise.  One workgroup per
+ * chunk. */
+int coocc_optim_adamw(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
+                      int nchunks, const float* coef, int write_grad, void* stream);
+/* g *= coef[0] in place on every element of every tensor (the stand-alone clip).  coef[0] == 1 stores nothing. */
+int coocc_optim_scale(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
+                      int nchunks, const float* coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
