@@ -216,6 +216,7 @@ SIGNATURES = {
     "coocc_optim_clip_coef": (I, [P, I, F, P, P, P, P]),
     "coocc_optim_adamw": (I, [P, P, I, P, I, P, I, P]),
     "coocc_optim_scale": (I, [P, P, I, P, I, P, P]),
+    "coocc_frames_to_imgs": (I, [P, P, I, I, I, P, P, P, L, I, I, P, P, P]),
 }
 
 _lib = None

@@ -1072,6 +1072,26 @@ int coocc_optim_adamw(const coocc_optim_tensor* tensors, const coocc_optim_tenso
 int coocc_optim_scale(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
                       int nchunks, const float* coef, void* stream);
 
+/* ---- camera img_inputs from decoded uint8 frames (co_occ_amd/image_inputs.py, csrc/image_inputs.hip): the per-pixel
+ * work of LoadMultiViewImageFromFiles_OccFormer (P/datasets/pipelines/loading_nusc_imgs.py:70-77, 185-188) with Pillow's bits.
+ * Per camera: Image.resize to (newW, newH) (bicubic, anti-aliased; integer arithmetic on the 22-bit fixed-point tables the host makes,
+ * horizontal pass first and rounded to uint8, a pass whose size does not change skipped), Image.crop at (crop_x0, crop_y0) with an
+ * fW x fH box and zeros outside the resized image, FLIP_LEFT_RIGHT when flip, then fp32 = byte / 255 (IEEE division).
+ *   frames      uint8 [N][Hs][Ws][3] contiguous, or NULL with frame_ptrs: N device addresses of [Hs][Ws][3] frames, in device memory
+ *   params      int32 [N][12] on the device: newW newH crop_x0 crop_y0 flip htab hk vtab vk 0 0 0.  htab / vtab: offset in ints of the
+ *               horizontal / vertical table in `tables`, or -1 for a skipped pass (then newW == Ws / newH == Hs); hk / vk its taps per index
+ *   params_host the same bytes in host memory: the entry checks every camera against them before it launches
+ *   tables      int32 [table_ints] on the device.  A table of `out` indices with k taps: out x (first source index, tap count), then
+ *               out x k taps (the unused ones 0).  May be NULL when no camera resizes
+ *   imgs        fp32 [N][3][fH][fW]; channel c is byte c of the frame (the reference never swaps mmcv's BGR)
+ *   canvas      optional uint8 [N][fH][fW][3]: the bytes imgs was divided from
+ * One launch, no atomics, the same bits from run to run.  A downscale ratio above 8 per axis (more than 33 taps) is refused.  The
+ * kernel clamps every table entry to the source, so a table that does not belong to its sizes gives wrong pixels, never a stray
+ * access.  No alignment is required of the frames. */
+int coocc_frames_to_imgs(const uint8_t* frames, const void* const* frame_ptrs, int N, int Hs, int Ws, const int32_t* params,
+                         const int32_t* params_host, const int32_t* tables, int64_t table_ints, int fH, int fW, float* imgs,
+                         uint8_t* canvas, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
