@@ -217,6 +217,7 @@ SIGNATURES = {
     "coocc_optim_adamw": (I, [P, P, I, P, I, P, I, P]),
     "coocc_optim_scale": (I, [P, P, I, P, I, P, P]),
     "coocc_frames_to_imgs": (I, [P, P, I, I, I, P, P, P, L, I, I, P, P, P]),
+    "coocc_points_to_depth_maps": (I, [P, L, I, P, I, I, I, P, P]),
 }
 
 _lib = None

@@ -314,6 +314,7 @@ class LoadMultiViewFrames:
         self._plans = collections.OrderedDict()
         self._stage = None
         self._stage_done = None
+        self._point_stage = None
 
     def choose_cams(self):
         cfg = self.data_config
@@ -351,11 +352,16 @@ class LoadMultiViewFrames:
         self._stage_done.record()
         return dev
 
-    def __call__(self, frames, cam_infos, lidar2cam_dic, flip=None, scale=None):
+    def __call__(self, frames, cam_infos, lidar2cam_dic, flip=None, scale=None, points=None):
         """``frames``: the decoded frames of the chosen cameras in the order of ``cam_names`` (a sequence, a [N,Hs,Ws,3] tensor, or a
         dict by camera name), uint8 with the channel order of the decoder -- channel k of ``imgs`` is byte k.  ``cam_infos``: the
         sample's ``['curr']['cams']`` dict; ``lidar2cam_dic``: 4 x 4 per camera name.  Returns ``(img_inputs, extras)``;
-        ``denorm_imgs`` (index 8) has the values of ``imgs`` and SHARES its storage."""
+        ``denorm_imgs`` (index 8) has the values of ``imgs`` and SHARES its storage.
+
+        ``points``: the key-frame cloud, fp32 [P,C>=3] (a device tensor, or a numpy array / CPU tensor that is uploaded).  With it
+        ``gt_depths`` (index 6) is the [N,fH,fW] LiDAR depth maps of the reference's CreateDepthFromLiDAR, made on the device
+        (``depth_maps``); the camera table rides in the one small upload and is ``extras['depth_table']``.  Without it
+        the slot holds the reference loader's [N,1] zeros."""
         cam_names = self.choose_cams()
         if isinstance(frames, dict):
             frames = [frames[c] for c in cam_names]
@@ -393,15 +399,25 @@ class LoadMultiViewFrames:
         imgs = frames_to_imgs(dev_frames, plan, canvas=canvas)
         # the small tensors: stacked on the host, one upload, views of it
         stacked = {k: torch.stack(v) for k, v in cols.items()}
+        if points is not None:
+            from . import depth_maps
+            stacked["depth_table"] = depth_maps.camera_table(*[stacked[k] for k in ("rots", "trans", "intrins", "post_rots", "post_trans")])
         flat = torch.cat([t.reshape(-1) for t in stacked.values()])
         flat = (flat.pin_memory() if self.device.type == "cuda" else flat).to(self.device, non_blocking=True)
         m, at = {}, 0
         for k, t in stacked.items():
             m[k] = flat[at:at + t.numel()].view(t.shape)
             at += t.numel()
-        img_inputs = (imgs, m["rots"], m["trans"], m["intrins"], m["post_rots"], m["post_trans"], m["gt_depths"], m["sensor2sensors"],
+        extras = dict(canvas=canvas, cam_names=cam_names, params=drawn, plan=plan)
+        gt_depths = m["gt_depths"]
+        if points is not None:
+            if self._point_stage is None:
+                self._point_stage = depth_maps.PointStage(self.device)
+            gt_depths = depth_maps.points_to_depth_maps(self._point_stage(points), m["depth_table"], (plan.fH, plan.fW))
+            extras["depth_table"] = m["depth_table"]
+        img_inputs = (imgs, m["rots"], m["trans"], m["intrins"], m["post_rots"], m["post_trans"], gt_depths, m["sensor2sensors"],
                       imgs, m["intrin_nerf"], m["c2ws"], imgs.shape[-2:])
-        return img_inputs, dict(canvas=canvas, cam_names=cam_names, params=drawn, plan=plan)
+        return img_inputs, extras
 
 
 def with_bda(img_inputs, bda_rot=None, aabb=None, batch=True):

@@ -1092,6 +1092,21 @@ int coocc_frames_to_imgs(const uint8_t* frames, const void* const* frame_ptrs, i
                          const int32_t* params_host, const int32_t* tables, int64_t table_ints, int fH, int fW, float* imgs,
                          uint8_t* canvas, void* stream);
 
+/* LiDAR depth maps from the raw point cloud (csrc/depth_maps.hip): the reference's CreateDepthFromLiDAR, lidar2depth.py:19-41, 63-85.
+ * Per point p and camera, in fp32 with every product rounded and the sums taken left to right (ATen's CPU bmm; no fused multiply-add):
+ *   q = p - tran;  c = inv_rot @ q;  k = intrin @ c;  d = k[2];  (u, v) = post_rot @ (k[0] / d, k[1] / d) + post_tran
+ * valid where u >= 0, v >= 0, u <= W-1, v <= H-1 and d > 0 on the unrounded values; the pixel is (rint(v), rint(u)), half to even.
+ * A pixel holds the MINIMUM d of the valid pairs that round to it and 0 where there is none (the reference's indexed assignment has no
+ * defined order where several do): the same bits from run to run and for every order of the points.
+ *   points  fp32 [P][point_stride] on the device, x y z first; point_stride >= 3 floats (nuScenes [P][5] clouds go in unsliced);
+ *           may be NULL when P == 0
+ *   cams    fp32 [N][28] on the device: inv_rot[9] tran[3] intrin[9] post_rot[0][0] [0][1] [1][0] [1][1] post_tran[0] [1] pad
+ *   maps    fp32 [N][H][W], written entirely
+ * A zero fill on `stream`, then one launch over the points (none when P == 0): a compare-and-swap minimum on the pixel's bits, no
+ * float atomics, no host read; capturable into a graph with no parallel branches. */
+int coocc_points_to_depth_maps(const float* points, int64_t P, int point_stride, const float* cams, int N, int H, int W, float* maps,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
