@@ -41,6 +41,9 @@ FINE2_IMG_INSIDE = __import__("os").environ.get("COOCC_FINE2_IMG_INSIDE", "1") =
 # occ_pred_conv[0] and the voxel half of fine_mlp[0] (both 128 -> 64 on out_voxel_feats) as one 128 -> 128 GEMM (ReLU on the first
 # 64 columns): one read of the rows and one launch instead of two; needs the strided-Q consumer (fine2_h2)
 MERGED_PRED_Q = __import__("os").environ.get("COOCC_MERGED_PRED_Q", "1") != "0"
+# the two-layer pointwise chains that end the coarse stage (occ_pred_conv with Q and the foreground flags; voxel_soft_weights) as
+# one launch each, hidden activation in LDS (csrc/head_tail_h2.hip); False = the layer-by-layer launches (same bits: A/B and tests)
+HEAD_TAIL_FUSED = True
 # pred_f of simple_test written output-major in one pass when the fine points are the head's own (coocc_scatter_fine_grouped);
 # 0 = fill + scatter by coordinates (coocc_scatter_fine[_dev])
 SCATTER_GROUPED = __import__("os").environ.get("COOCC_SCATTER_GROUPED", "1") != "0"
@@ -174,8 +177,10 @@ class OccHead(nn.Module):
         occs = [o0] + small
         wlogit = None
         if self.soft_weights:
-            h = conv_rows(o0, p["soft"][0], relu=True)
-            wlogit = conv_rows(h, p["soft"][1], relu=False).t
+            wlogit = self._soft_tail(o0, p["soft"])
+            if wlogit is None:
+                h = conv_rows(o0, p["soft"][0], relu=True)
+                wlogit = conv_rows(h, p["soft"][1], relu=False).t
         lbr.join(*[o.t for o in small])
         L = len(occs)
         levels = (_lib.c_void_p * L)(*[o.t.data_ptr() for o in occs])
@@ -188,6 +193,10 @@ class OccHead(nn.Module):
         if core.wants_h2_twin(out, (first,)):
             tw = out.h2 = torch.empty_like(o0.t)
         call("coocc_occhead_mix_ex", levels, dims, L, ptr(wlogit), ptr(out.t), o0.B, o0.C, ptr(tw))
+        if merged and tw is not None:
+            occ = self._pred_tail(out, first, p["pred"][1])   # one launch down to the logits and the foreground flags
+            if occ is not None:
+                return out, occ
         if merged:
             hq = conv_rows(out, first, relu=64)               # [V, 128] = relu(bn(pred0 x)) | Q = W_f0[:, :128] x
             h = Rows(hq.t, hq.B, hq.X, hq.Y, hq.Z, 64, 0)
@@ -196,6 +205,47 @@ class OccHead(nn.Module):
             h = conv_rows(out, p["pred"][0], relu=True)
         occ = conv_rows(h, p["pred"][1], relu=False)
         return out, occ
+
+    def _tail_engine_ok(self):
+        from . import core
+        return HEAD_TAIL_FUSED and not self.training and core.CONV_ENGINE == "h2" and core.CONV_DTYPE == "f32"
+
+    def _soft_tail(self, o0, soft):
+        """voxel_soft_weights (128 -> 64 BN ReLU -> L) in one launch (csrc/head_tail_h2.hip), when its two layers take the
+        split-f16 pointwise GEMM and the fp32-MFMA 32-column kernel today: the bits of those launches.  None = not taken."""
+        from . import core
+        s0, s1 = soft
+        g = (o0.B, o0.X, o0.Y, o0.Z)
+        if not (self._tail_engine_ok() and o0.C == 128 and o0.coff == 0 and s0.Cin == 128 and s0.Cout == 64 and s1.Cin == 64 and s1.Cout <= 32
+                and s0.scale is not None and s1.scale is None and s0.is_pointwise and s1.is_pointwise
+                and core.route(*g, s0) == "h2" and core.route(*g, s1) == "other"):
+            return None
+        M = o0.B * o0.V
+        wlogit = torch.empty(M, s1.Cout, device=o0.t.device, dtype=_F32)
+        with TIMER.region("k_head_soft_h2", 2.0 * M * 64 * (128 + s1.Cout)):
+            call("coocc_head_soft_h2", ptr(core.h2_rows(o0)), 128, M, None, ptr(s0.h2_pack()), ptr(s0.scale), ptr(s0.bias), None, 0,
+                 ptr(s1.w), ptr(s1.bias), s1.Cout, ptr(wlogit), s1.Cout)
+        return wlogit
+
+    def _pred_tail(self, out, pq, p1):
+        """The merged occ_pred_conv[0] | Q layer, occ_pred_conv[3] and the fine branch's foreground flags in one launch
+        (csrc/head_tail_h2.hip), when both layers take the split-f16 GEMMs today: the bits of those launches.  ``out.h2`` is the
+        mix kernel's twin.  Returns the logits Rows (``aux``: the flags), or None = not taken."""
+        from . import core
+        g = (out.B, out.X, out.Y, out.Z)
+        if not (self._tail_engine_ok() and out.C == 128 and pq.Cout == 128 and p1.Cin == 64 and p1.Cout <= 32 and p1.scale is None
+                and p1.is_pointwise and core.route(*g, pq) == "h2" and core.route(*g, p1) == "h2"):
+            return None
+        M, dev = out.B * out.V, out.t.device
+        hq = torch.empty(M, 128, device=dev, dtype=_F32)      # columns 64..127 = Q; the hidden half stays in LDS (never written here)
+        occ = Rows(torch.empty(M, p1.Cout, device=dev, dtype=_F32), out.B, out.X, out.Y, out.Z, p1.Cout)
+        flags = torch.empty(M, device=dev, dtype=torch.uint8)
+        with TIMER.region("k_head_pred_h2", 2.0 * M * (128 * 128 + 64 * p1.Cout)):
+            call("coocc_head_pred_h2", ptr(out.h2), 128, M, None, ptr(pq.h2_pack()), ptr(pq.scale), ptr(pq.bias), ptr(hq), 128, 0,
+                 ptr(p1.h2_pack()), ptr(p1.bias), p1.Cout, ptr(occ.t), p1.Cout, self.empty_idx, ptr(flags))
+        out.aux = dict(q=hq[:, 64:])                          # rows 128 floats apart: csrc/fine2_h2.hip takes the stride
+        occ.aux = dict(flags=flags)                           # argmax != empty_idx of these logits (``_fine``)
+        return occ
 
     def level_readers(self):
         """Per input level, the layers that read it (the neck's fpn_convs write H2 twins for the split-f16 ones)."""
@@ -243,8 +293,10 @@ class OccHead(nn.Module):
         dev = ovf.t.device
         V, r = ovf.V, self.cascade_ratio
         assert ovf.B == 1, "OccHead fine branch: B == 1 (as the render block asserts, coocc_ray.py:571)"
-        flags = torch.empty(V, device=dev, dtype=torch.uint8)
-        call("coocc_argmax_flags", ptr(occ.t), V, occ.C, occ.stride, self.empty_idx, ptr(flags))
+        flags = occ.aux.get("flags") if occ.aux else None     # written with the logits by the one-launch head tail
+        if flags is None:
+            flags = torch.empty(V, device=dev, dtype=torch.uint8)
+            call("coocc_argmax_flags", ptr(occ.t), V, occ.C, occ.stride, self.empty_idx, ptr(flags))
         lin = torch.empty(V, device=dev, dtype=_I32)
         cnt = torch.empty(1, device=dev, dtype=_I32)
         ws = torch.empty(V // 1024 + 2, device=dev, dtype=_I32)

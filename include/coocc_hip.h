@@ -332,6 +332,26 @@ int coocc_render_heads_h2(const void* x_h2, int V, int Cin, int width, const voi
                           const float* ws1, const float* bs1, const void* const* wr_packs_host,
                           const float* const* br_host, int n_rgb_hidden, const float* wr_out, const float* br_out,
                           float* table, int activate, void* stream);
+/* The two-layer pointwise chains that end OccHead's coarse stage (occ_head.py:149-171, :182), ONE launch each with the hidden
+ * activation in LDS (csrc/head_tail_h2.hip); every output holds the bits of the launches it replaces.
+ * coocc_head_pred_h2: x_h2 = H2 rows [rows][in_stride] (first 128 channels); w1_pack / scale1 / bias1 = the merged 128 -> 128
+ * layer (occ_pred_conv[0] with folded BN | voxel half of fine_mlp[0]; mfma_dtype 3 pack); hq [rows][hq_stride >= 128] fp32:
+ * columns 64..127 (Q) are always written, columns 0..63 (the ReLU'd hidden activation) only when write_hidden != 0; w2_pack =
+ * occ_pred_conv[3] (64 -> ncls <= 32, mfma_dtype 3 pack), bias2 or NULL; logits [rows][logit_stride]; flags (or NULL): one byte
+ * per row, argmax(logits) != empty_idx with the first maximum winning (coocc_argmax_flags).  The hidden activation is checked
+ * against the operand range of the split-f16 engine (coocc_h2_overflow).  Replaces coocc_conv_fwd + coocc_rows_to_h2 +
+ * coocc_conv_fwd + coocc_argmax_flags.
+ * coocc_head_soft_h2: voxel_soft_weights: w1_pack / scale1 / bias1 = layer 0 (128 -> 64, folded BN, ReLU; mfma_dtype 3 pack),
+ * w2_pack = layer 3 (64 -> L <= 32) in the fp32 pack of coocc_conv_pack_weights, bias2 or NULL; wlogit [rows][wlogit_stride];
+ * hidden (or NULL): the fp32 hidden activation [rows][hidden_stride >= 64].  Replaces two coocc_conv_fwd launches.
+ * rows_dev (or NULL): the row count on the device (<= rows, the capacity the grid is sized for); rows past it are not written. */
+int coocc_head_pred_h2(const void* x_h2, int in_stride, int rows, const int32_t* rows_dev, const void* w1_pack,
+                       const float* scale1, const float* bias1, float* hq, int hq_stride, int write_hidden,
+                       const void* w2_pack, const float* bias2, int ncls, float* logits, int logit_stride,
+                       int empty_idx, uint8_t* flags, void* stream);
+int coocc_head_soft_h2(const void* x_h2, int in_stride, int rows, const int32_t* rows_dev, const void* w1_pack,
+                       const float* scale1, const float* bias1, float* hidden, int hidden_stride, const void* w2_pack,
+                       const float* bias2, int L, float* wlogit, int wlogit_stride, void* stream);
 /* coocc_wino_pack_weights_dev for the split-f16 engine (mfma_dtype 3): U = G g G^T in fp64, split into f16 hi / lo, in the H2 pack
  * layout [(tile+2)^2][(K chunk, dz)][roundup(N,128)/32][2 k16 steps][hi | lo][64 lanes][8 f16].  The GEMM's K (Cin forward, Cout
  * dgrad) must be a multiple of 32.  packed == NULL: returns the size in 4-byte units.  Lets the TRAINING path (which re-packs from
