@@ -31,6 +31,7 @@ from . import depth_net
 from .depth_net import DepthNet
 from .evaluation import SemanticEvaluator, cm_to_ious, evaluation_semantic
 from . import optim
+from . import occ_gt
 
 register_into_mmdet()
 

@@ -220,6 +220,13 @@ SIGNATURES = {
     "coocc_optim_scale": (I, [P, P, I, P, I, P, P]),
     "coocc_frames_to_imgs": (I, [P, P, I, I, I, P, P, P, L, I, I, P, P, P]),
     "coocc_points_to_depth_maps": (I, [P, L, I, P, I, I, I, P, P]),
+    "coocc_occ_scatter_labels": (I, [P, L, I, I, I, I, P, P, P]),
+    "coocc_occ_rows_to_voxels": (I, [P, L, P, P, I, I, I, P, P, P, P]),
+    "coocc_occ_points_to_voxels": (I, [P, L, I, P, P, P, P, I, I, I, I, P, P, P, P]),
+    "coocc_occ_vote_ws": (Z, [L]),
+    "coocc_occ_vote_labels": (I, [P, P, L, L, I, I, P, P, Z, P]),
+    "coocc_occ_visible_rows": (I, [P, L, P, I, I, I, P, P, P]),
+    "coocc_occ_cloud_aabb": (I, [P, L, I, P, P, P, P]),
 }
 
 _lib = None

@@ -19,8 +19,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # render_eval.hip: the uint8 comparison panels restate the reference's fp32 expression in its order and must give the CPU's bytes.
 # depth_maps.hip: the LiDAR projection restates ATen's CPU bmm of 3 x 3 matrices -- every product rounded, sums left to right -- so the
 # pixel a point rounds to is the CPU's; a contracted chain moves one written pixel in six.
+# occ_gt.hip: the occupancy ground truth is integers decided by floats -- a voxel index from a float64 centre rounded to fp32,
+# rotated in fp32 and divided in float64, a pixel and d*10 from depth_maps.hip's projection chain, a box from two float64 transforms --
+# and each is rounded where numpy and ATen's CPU code round it; a contracted multiply-add moves a centre across a voxel border
+# (DESIGN.md 16).
 FILE_FLAGS = {"fine_fused.hip": ["-fno-slp-vectorize"], "lidarseg.hip": ["-ffp-contract=off"],
-              "render_eval.hip": ["-ffp-contract=off"], "depth_maps.hip": ["-ffp-contract=off"]}
+              "render_eval.hip": ["-ffp-contract=off"], "depth_maps.hip": ["-ffp-contract=off"], "occ_gt.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -76,14 +76,49 @@ def points_to_depth_maps(points, table, size, out=None):
     return out
 
 
-class PointStage:
-    """Host points (a numpy array or a CPU tensor, fp32 ``[P,C]``) -> the device through one pinned staging buffer and one asynchronous
-    copy, as the loader uploads frames; device points pass through.  The buffer grows to the largest cloud seen and is reused once the
-    previous copy has read it."""
+class HostStage:
+    """Several host arrays (numpy, contiguous or made so, any dtype) -> the device through ONE pinned staging buffer and one
+    asynchronous copy: they are laid into the buffer at 256-byte offsets and the device tensors returned are views of that one
+    upload (uint16 arrays come back as int16 views of the same bits: torch has no uint16 views).  The buffer grows to the largest
+    sample seen and is reused once the previous copy has read it.  ``last_bytes``: the bytes of the last upload."""
 
     def __init__(self, device):
         self.device = torch.device(device)
-        self._stage, self._done = None, None
+        self._stage, self._done, self.last_bytes = None, None, 0
+
+    def __call__(self, arrays):
+        if self.device.type != "cuda":
+            raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % self.device)
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        offs, at = [], 0
+        for a in arrays:
+            offs.append(at)
+            at += (a.nbytes + 255) & ~255
+        self.last_bytes = at
+        dtypes = [torch.int16 if a.dtype == np.uint16 else torch.from_numpy(np.empty(0, a.dtype)).dtype for a in arrays]
+        if at == 0:
+            return [torch.empty(a.shape, dtype=dt, device=self.device) for a, dt in zip(arrays, dtypes)]
+        if self._stage is None or self._stage.numel() < at:
+            self._stage = torch.empty(at, dtype=torch.uint8).pin_memory()
+        elif self._done is not None:
+            self._done.synchronize()                             # the previous sample's copy has read the buffer
+        host = self._stage.numpy()
+        for a, o in zip(arrays, offs):
+            host[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        dev = self._stage[:at].to(self.device, non_blocking=True)
+        self._done = torch.cuda.Event()
+        self._done.record()
+        return [dev[o:o + a.nbytes].view(dt).view(a.shape) for a, o, dt in zip(arrays, offs, dtypes)]
+
+
+class PointStage:
+    """Host points (a numpy array or a CPU tensor, fp32 ``[P,C]``) -> the device through one pinned staging buffer and one asynchronous
+    copy, as the loader uploads frames; device points pass through.  The buffer grows to the largest cloud seen and is reused once the
+    previous copy has read it (``HostStage`` with one array)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._host = HostStage(device)
 
     def __call__(self, points):
         if isinstance(points, np.ndarray):
@@ -98,19 +133,9 @@ class PointStage:
             return points
         if self.device.type != "cuda":
             raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % self.device)
-        n = points.numel()
-        if n == 0:
+        if points.numel() == 0:
             return torch.empty(tuple(points.shape), dtype=torch.float32, device=self.device)
-        if self._stage is None or self._stage.numel() < n:
-            self._stage = torch.empty(n, dtype=torch.float32).pin_memory()
-        elif self._done is not None:
-            self._done.synchronize()                             # the previous sample's copy has read the buffer
-        host = self._stage[:n].view(points.shape)
-        host.copy_(points)
-        dev = host.to(self.device, non_blocking=True)
-        self._done = torch.cuda.Event()
-        self._done.record()
-        return dev
+        return self._host([points.detach().contiguous().numpy()])[0]
 
 
 def lidar_gt_depths(nine, bda_rot=None, batch=True):

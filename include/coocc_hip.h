@@ -1127,6 +1127,51 @@ int coocc_frames_to_imgs(const uint8_t* frames, const void* const* frame_ptrs, i
 int coocc_points_to_depth_maps(const float* points, int64_t P, int point_stride, const float* cams, int N, int H, int W, float* maps,
                                void* stream);
 
+/* ---- occupancy ground truth from the annotation rows (co_occ_amd/occ_gt.py, csrc/occ_gt.hip): gt_occ, the visibility
+ * masks, points_occ and aabb of the reference's LoadOccupancy, LoadOccupancy2 (P/datasets/pipelines/loading.py) and
+ * LoadNuscOccupancyAnnotations (loading_nusc_occ.py) with the reference's integers.  `rows` is uint16 [N][4] on the device: the three
+ * index columns as the file has them and the label (0 .. 255).  Grids have 1 .. 65535 cells per side and 2^24 voxels at most.  Every
+ * entry works on `stream`, reads nothing back, and writes no voxel outside the volume whatever the rows hold; the arguments called
+ * "host" are read before the entry returns.
+ *
+ * occ_scatter_labels (LoadOccupancy): vol[i0][i1][i2] = label, 0 where no row points; THE LAST ROW of a voxel wins (numpy's indexed
+ *   assignment), independent of the thread order.  use_semantic: label 0 is written as 255; without it rows of label 0 are skipped
+ *   and the others write 1.  win: uint32 [G0*G1*G2] scratch.  N < 2^24 - 1.  A fill, a launch over the rows, one over the volume. */
+int coocc_occ_scatter_labels(const uint16_t* rows, int64_t N, int G0, int G1, int G2, int use_semantic, uint32_t* win, uint8_t* vol,
+                             void* stream);
+/* occ_rows_to_voxels (LoadOccupancy2): per row the float64 centre (idx[[2,1,0]] + 0.5) * voxel_size + lo, rounded to fp32 (centres
+ *   fp32 [N][3], optional: what project_points reads), bda @ centre in fp32 (products rounded, sums left to right), in float64
+ *   (x - lo) / voxel_size, clipped to [0, G-1], truncated -> vox int32 [N] (linear, x-major); labels uint8 [N]: the label, 0 as 255.
+ *   grid: host doubles lo[3] voxel_size[3]; bda: host fp32 [9] row-major, NULL for the identity. */
+int coocc_occ_rows_to_voxels(const uint16_t* rows, int64_t N, const double* grid, const float* bda, int G0, int G1, int G2, int32_t* vox,
+                             uint8_t* labels, float* centres, void* stream);
+/* occ_points_to_voxels: one thread per point of fp32 [P][point_stride].  t = p @ bda^T in fp32; label = table[seg[i]] (0 without seg);
+ *   points_occ fp32 [P][4] = (t, label) when given.  mode 0: nothing else.  mode 1 (LoadNuscOccupancyAnnotations): vox =
+ *   floor((clip(t, lo, hi) - lo) / voxel_size) in float64 with hi the host's upper bound minus 1e-5, -1 for a non-finite point.
+ *   mode 2 (the LiDAR visibility voxels): points p with lo <= p < hi on all axes, (p - lo) / voxel_size truncated, label 1; others -1.
+ *   grid: host doubles lo[3] hi[3] voxel_size[3]; seg uint8 [P], table uint8 [256] on the device. */
+int coocc_occ_points_to_voxels(const float* points, int64_t P, int point_stride, const uint8_t* seg, const uint8_t* table, const float* bda,
+                               const double* grid, int G0, int G1, int G2, int mode, int32_t* vox, uint8_t* labels, float* points_occ,
+                               void* stream);
+/* occ_vote_labels (nb_process_label): vol uint8 [V] = fill, then for every voxel that has rows the label with the largest count
+ *   MODULO 65 536 (the reference's uint16 counter), the lowest label among equals (np.argmax; 0 when every count wraps to 0).  Rows
+ *   with vox < 0 or >= V do not vote.  post_empty >= 0: a written vote of 0 becomes 255, then one equal to post_empty becomes 0
+ *   (pass the fill already mapped).  Keys vox * 256 + label, one rocprim radix sort, one run-length pass: no atomics on the volume,
+ *   the same bytes for every row order.  ws: coocc_occ_vote_ws(N) bytes. */
+size_t coocc_occ_vote_ws(int64_t N);
+int coocc_occ_vote_labels(const int32_t* vox, const uint8_t* labels, int64_t N, int64_t V, int fill, int post_empty, uint8_t* vol, void* ws,
+                          size_t ws_bytes, void* stream);
+/* occ_visible_rows (LoadOccupancy2, cal_visible; nb_process_img_points): flags uint8 [N] = 1 where the centre wins a pixel in any
+ *   camera.  The projection is coocc_points_to_depth_maps' chain and its [ncam][28] table; a pair counts where 0 <= u < W, 0 <= v < H,
+ *   d >= 0; its pixel is (u, v) truncated and its depth d * 10 truncated; the pixel's winner is the lexicographic minimum of
+ *   (depth, row) among depths below 2048 (a 64-bit atomicMin).  canvas: uint64 [ncam][H][W] scratch.  H, W <= 32767. */
+int coocc_occ_visible_rows(const float* centres, int64_t N, const float* cams, int ncam, int H, int W, uint64_t* canvas, uint8_t* flags,
+                           void* stream);
+/* occ_cloud_aabb: aabb fp32 [2][3] = min / max over the points of r2 @ (r1 @ p + t1) + t2 in float64 (products rounded, sums left to
+ *   right), rounded once to fp32; an axis on which any transformed value is NaN gives NaN for its min and max, as numpy's do.  transforms: host doubles r1[9] t1[3] r2[9] t2[3]; slots: uint64 [6] scratch.  P >= 1. */
+int coocc_occ_cloud_aabb(const float* points, int64_t P, int point_stride, const double* transforms, uint64_t* slots, float* aabb,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
