@@ -218,6 +218,9 @@ SIGNATURES = {
     "coocc_optim_clip_coef": (I, [P, I, F, P, P, P, P]),
     "coocc_optim_adamw": (I, [P, P, I, P, I, P, I, P]),
     "coocc_optim_scale": (I, [P, P, I, P, I, P, P]),
+    "coocc_optim_pack": (I, [P, P, I, P, I, P, L, I, P]),
+    "coocc_optim_unpack": (I, [P, P, I, P, I, P, L, P]),
+    "coocc_optim_flag_check": (I, [P, I, P, I, P, P]),
     "coocc_frames_to_imgs": (I, [P, P, I, I, I, P, P, P, L, I, I, P, P, P]),
     "coocc_points_to_depth_maps": (I, [P, L, I, P, I, I, I, P, P]),
     "coocc_occ_scatter_labels": (I, [P, L, I, I, I, I, P, P, P]),

@@ -3,7 +3,9 @@
 // co_occ_amd/optim.py fills the tables).
 //
 // k_optim_sumsq (one fp64 partial per chunk) -> k_optim_clip_coef (partials added in a fixed order; norm and coefficient) ->
-// k_optim_adamw (coefficient applied in registers, then the update) | k_optim_scale (the stand-alone clip).
+// k_optim_adamw (coefficient applied in registers, then the update) | k_optim_scale (the stand-alone clip).  In front of them, with a
+// process group: k_optim_pack (every gradient / world into one arena) -> the all-reduce -> k_optim_flag_check; k_optim_unpack is
+// the copy back.
 // A chunk is OPT_CHUNK consecutive elements of one tensor, cut into groups of four: thread t of the workgroup owns groups t, t + 256,
 // ...  That ownership is the same whatever the pointers' alignment -- an aligned chunk reads a group as one 16-byte load, any other
 // chunk as four 4-byte loads, the tensor's last incomplete group always element by element -- so the order of every sum depends on the
@@ -179,6 +181,71 @@ __global__ __launch_bounds__(OPT_THREADS) void k_optim_scale(const coocc_optim_t
   }
 }
 
+// ------------------------------------------------------------------ data-parallel gradient averaging
+// The arena is one fp32 buffer: a header of one float per layout tensor, then one segment per tensor at a multiple of four elements.
+// In the tables of these kernels one of the two pointers of an entry is the tensor's arena segment: p for pack (g is the source, NULL:
+// this rank has no gradient), g for unpack (p is the destination).  The arena side is 16-byte aligned by construction; the other side
+// picks 16- or 4-byte accesses by its pointer.  The padding between segments is never written.
+__global__ __launch_bounds__(OPT_THREADS) void k_optim_pack(const coocc_optim_tensor* __restrict__ tensors, int ntensors,
+                                                             const long long* __restrict__ chunks, float* __restrict__ header,
+                                                             float world) {
+  const OptSpan s = opt_span(tensors, ntensors, chunks);
+  if (s.ti < 0) return;
+  const float* src = tensors[s.ti].g;
+  float* __restrict__ dst = tensors[s.ti].p + s.off;
+  if (s.off == 0 && threadIdx.x == 0) header[s.ti] = src ? 1.f : 0.f;       // the presence flag: never divided
+  const float* __restrict__ g = src ? src + s.off : nullptr;
+  const bool vec = g && al16(g);
+  const int ngroups = (s.n + 3) >> 2;
+#pragma unroll 4
+  for (int q = threadIdx.x; q < ngroups; q += OPT_THREADS) {
+    const int base = q << 2, k = s.n - base < 4 ? s.n - base : 4;
+    op_f4 gv = {0.f, 0.f, 0.f, 0.f};
+    if (g) {
+      gv = load4(g, base, k, vec);
+      if (world != 1.f) {                        // world == 1 copies the bits
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gv[e] = __fdiv_rn(gv[e], world);        // correctly rounded: DDP divides
+      }
+    }
+    store4(dst, base, k, true, gv);
+  }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void k_optim_unpack(const coocc_optim_tensor* __restrict__ tensors, int ntensors,
+                                                               const long long* __restrict__ chunks) {
+  const OptSpan s = opt_span(tensors, ntensors, chunks);
+  if (s.ti < 0) return;
+  const float* __restrict__ src = tensors[s.ti].g + s.off;
+  float* __restrict__ dst = tensors[s.ti].p + s.off;
+  const bool vec = al16(dst);
+  const int ngroups = (s.n + 3) >> 2;
+#pragma unroll 4
+  for (int q = threadIdx.x; q < ngroups; q += OPT_THREADS) {
+    const int base = q << 2, k = s.n - base < 4 ? s.n - base : 4;
+    store4(dst, base, k, vec, load4(src, base, k, true));
+  }
+}
+
+// one workgroup over pack's tensor table after the reduce: header[i] is the number of ranks that had a gradient for tensor i, a small
+// integer and exact in fp32; every rank presenting the same set means world where this rank had one and 0 where it had none.  The count
+// of the others is ADDED to the sticky word by one thread (launches on a stream are ordered: no atomic needed).
+__global__ __launch_bounds__(OPT_THREADS) void k_optim_flag_check(const coocc_optim_tensor* __restrict__ tensors, int ntensors,
+                                                                   const float* __restrict__ header, float world,
+                                                                   int* __restrict__ sticky) {
+  __shared__ int s_a[OPT_THREADS / 64];
+  const int tid = threadIdx.x;
+  int bad = 0;
+  for (int i = tid; i < ntensors; i += OPT_THREADS) {
+    const float want = tensors[i].g ? world : 0.f;
+    bad += header[i] != want ? 1 : 0;            // a NaN counts
+  }
+  for (int m = 32; m > 0; m >>= 1) bad += __shfl_xor(bad, m);
+  if ((tid & 63) == 0) s_a[tid >> 6] = bad;
+  __syncthreads();
+  if (tid == 0) sticky[0] += s_a[0] + s_a[1] + s_a[2] + s_a[3];
+}
+
 // what the host can check of the tables before a launch: the tensor table's host copy gives every numel and pointer, and with them the
 // chunk count the chunk table must have.  Returns nullptr or the complaint.
 static const char* opt_check(const coocc_optim_tensor* tensors, const coocc_optim_tensor* th, int ntensors, const int64_t* chunks,
@@ -198,9 +265,66 @@ static const char* opt_check(const coocc_optim_tensor* tensors, const coocc_opti
   return nullptr;
 }
 
+// the same for the tables of pack (the arena side is p, the tensor side g and may be NULL) and unpack (the arena side is g): every
+// segment 16-byte aligned and wholly inside [arena + header, arena + arena_numel), segments in ascending order without overlap
+static const char* opt_check_arena(const coocc_optim_tensor* tensors, const coocc_optim_tensor* th, int ntensors, const int64_t* chunks,
+                                   int nchunks, const float* arena, int64_t arena_numel, int64_t header, bool pack) {
+  if (!tensors || !th || !chunks) return "null table";
+  if (ntensors <= 0 || nchunks <= 0) return "ntensors and nchunks must be positive";
+  if (!arena || ((uintptr_t)arena & 15)) return "a null or misaligned arena";
+  if (header < 0 || arena_numel < header) return "an arena shorter than its header";
+  const uintptr_t lo = (uintptr_t)arena + 4 * (uintptr_t)header, hi = (uintptr_t)arena + 4 * (uintptr_t)arena_numel;
+  uintptr_t prev = lo;
+  int64_t want = 0;
+  for (int i = 0; i < ntensors; ++i) {
+    const coocc_optim_tensor& t = th[i];
+    if (t.numel <= 0) return "a tensor with numel <= 0";
+    const uintptr_t seg = (uintptr_t)(pack ? t.p : t.g), other = (uintptr_t)(pack ? t.g : t.p);
+    if (!seg || (seg & 15)) return "an arena segment that is null or not 16-byte aligned";
+    if (seg < prev || seg > hi || (uint64_t)t.numel > (hi - seg) / 4) return "an arena segment outside the arena or not in ascending order";
+    prev = seg + 4 * (uintptr_t)t.numel;
+    if (pack ? (other & 3) != 0 : (!other || (other & 3))) return pack ? "a misaligned gradient pointer" : "a null or misaligned destination";
+    want += (t.numel + OPT_CHUNK - 1) / OPT_CHUNK;
+  }
+  if (want != (int64_t)nchunks) return "nchunks is not the chunk count of the tensor table";
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" int coocc_optim_chunk(void) { return OPT_CHUNK; }
+
+extern "C" int coocc_optim_pack(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors,
+                                const int64_t* chunks, int nchunks, float* arena, int64_t arena_numel, int world, void* stream) {
+  const char* why = opt_check_arena(tensors, tensors_host, ntensors, chunks, nchunks, arena, arena_numel, ntensors, true);
+  COOCC_CHECK_ARG(!why, "optim_pack: %s (ntensors=%d nchunks=%d)", why, ntensors, nchunks);
+  COOCC_CHECK_ARG(world >= 1 && world <= (1 << 24), "optim_pack: world = %d (1 .. 2^24)", world);
+  hipLaunchKernelGGL(k_optim_pack, dim3(nchunks), dim3(OPT_THREADS), 0, as_stream(stream), tensors, ntensors, (const long long*)chunks,
+                     arena, (float)world);
+  COOCC_LAUNCH_CHECK("k_optim_pack");
+  return COOCC_OK;
+}
+
+extern "C" int coocc_optim_unpack(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors,
+                                  const int64_t* chunks, int nchunks, const float* arena, int64_t arena_numel, void* stream) {
+  const char* why = opt_check_arena(tensors, tensors_host, ntensors, chunks, nchunks, arena, arena_numel, 0, false);
+  COOCC_CHECK_ARG(!why, "optim_unpack: %s (ntensors=%d nchunks=%d)", why, ntensors, nchunks);
+  hipLaunchKernelGGL(k_optim_unpack, dim3(nchunks), dim3(OPT_THREADS), 0, as_stream(stream), tensors, ntensors,
+                     (const long long*)chunks);
+  COOCC_LAUNCH_CHECK("k_optim_unpack");
+  return COOCC_OK;
+}
+
+extern "C" int coocc_optim_flag_check(const coocc_optim_tensor* tensors, int ntensors, const float* header, int world, int* sticky,
+                                      void* stream) {
+  COOCC_CHECK_ARG(tensors && header && sticky, "optim_flag_check: null pointer");
+  COOCC_CHECK_ARG(ntensors > 0, "optim_flag_check: ntensors = %d (positive)", ntensors);
+  COOCC_CHECK_ARG(world >= 1 && world <= (1 << 24), "optim_flag_check: world = %d (1 .. 2^24)", world);
+  hipLaunchKernelGGL(k_optim_flag_check, dim3(1), dim3(OPT_THREADS), 0, as_stream(stream), tensors, ntensors, header, (float)world,
+                     sticky);
+  COOCC_LAUNCH_CHECK("k_optim_flag_check");
+  return COOCC_OK;
+}
 
 extern "C" int coocc_optim_sumsq(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors,
                                  const int64_t* chunks, int nchunks, double* partials, void* stream) {

@@ -1091,6 +1091,23 @@ int coocc_optim_adamw(const coocc_optim_tensor* tensors, const coocc_optim_tenso
 /* g *= coef[0] in place on every element of every tensor (the stand-alone clip).  coef[0] == 1 stores nothing. */
 int coocc_optim_scale(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
                       int nchunks, const float* coef, void* stream);
+/* Data-parallel gradient averaging.  The arena is one fp32 buffer of arena_numel elements, 16-byte aligned: a header
+ * of one float per layout tensor, then one segment per tensor, each at a multiple of four elements, ascending, without overlap.
+ * The tables are the ones above; one pointer of every entry is the tensor's arena segment, which the entries check against the
+ * arena's bounds before they launch.
+ * pack: entry i of the table is layout tensor i; p = its segment, g = this rank's gradient or NULL.  segment = g / world in fp32,
+ * correctly rounded (world == 1: the bits), zeros where g is NULL; arena[i] = 1.0 where g is there, 0.0 where not (never divided).
+ * The padding between segments is not written.  One workgroup per chunk. */
+int coocc_optim_pack(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
+                     int nchunks, float* arena, int64_t arena_numel, int world, void* stream);
+/* unpack: g = the segment, p = the destination (fp32, contiguous, 4-byte aligned); the bits of the segment are copied.  The table
+ * may hold any subset of the layout in layout order. */
+int coocc_optim_unpack(const coocc_optim_tensor* tensors, const coocc_optim_tensor* tensors_host, int ntensors, const int64_t* chunks,
+                       int nchunks, const float* arena, int64_t arena_numel, void* stream);
+/* After the all-reduce of the arena: header[i] is the number of ranks that had a gradient for tensor i.  sticky[0] += the number
+ * of i in [0, ntensors) with header[i] != (tensors[i].g ? world : 0), `tensors` being pack's device table.  One workgroup. */
+int coocc_optim_flag_check(const coocc_optim_tensor* tensors, int ntensors, const float* header, int world, int* sticky,
+                           void* stream);
 
 /* ---- camera img_inputs from decoded uint8 frames (co_occ_amd/image_inputs.py, csrc/image_inputs.hip): the per-pixel
  * work of LoadMultiViewImageFromFiles_OccFormer (P/datasets/pipelines/loading_nusc_imgs.py:70-77, 185-188) with Pillow's bits.
