@@ -32,6 +32,7 @@ from .depth_net import DepthNet
 from .evaluation import SemanticEvaluator, cm_to_ious, evaluation_semantic
 from . import optim
 from . import occ_gt
+from . import sweeps
 
 register_into_mmdet()
 

@@ -230,6 +230,8 @@ SIGNATURES = {
     "coocc_occ_vote_labels": (I, [P, P, L, L, I, I, P, P, Z, P]),
     "coocc_occ_visible_rows": (I, [P, L, P, I, I, I, P, P, P]),
     "coocc_occ_cloud_aabb": (I, [P, L, I, P, P, P, P]),
+    "coocc_sweeps_merge_ws": (Z, [L]),
+    "coocc_sweeps_merge": (I, [P, L, I, P, P, I, P, I, F, P, L, P, P, Z, P]),
 }
 
 _lib = None

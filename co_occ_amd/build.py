@@ -23,8 +23,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # rotated in fp32 and divided in float64, a pixel and d*10 from depth_maps.hip's projection chain, a box from two float64 transforms --
 # and each is rounded where numpy and ATen's CPU code round it; a contracted multiply-add moves a centre across a voxel border
 # (DESIGN.md 16).
+# sweeps.hip: the sweep transform restates numpy's float64 xyz @ R.T and + t with a rounding to fp32 after each -- every product
+# rounded in fp64, sums left to right; a contracted multiply-add moves a coordinate that sits near an fp32 rounding boundary
+# (DESIGN.md 18).
 FILE_FLAGS = {"fine_fused.hip": ["-fno-slp-vectorize"], "lidarseg.hip": ["-ffp-contract=off"],
-              "render_eval.hip": ["-ffp-contract=off"], "depth_maps.hip": ["-ffp-contract=off"], "occ_gt.hip": ["-ffp-contract=off"]}
+              "render_eval.hip": ["-ffp-contract=off"], "depth_maps.hip": ["-ffp-contract=off"], "occ_gt.hip": ["-ffp-contract=off"],
+              "sweeps.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -1,6 +1,6 @@
 """LiDAR depth maps from the raw point cloud.
 
-The reference's CreateDepthFromLiDAR (P/datasets/pipelines/lidar2depth.py) projects the key-frame cloud into every camera with
+The reference's CreateDepthFromLiDAR (P/datasets/pipelines/lidar2depth.py) projects the cloud (key frame, or the merged sweeps) into every camera with
 broadcast fp32 matmuls on the CPU, sorts per camera and fills ``[N,fH,fW]`` maps with an indexed assignment; the maps then travel to
 the device (34 MB at 6 x 896 x 1600).  Here the cloud goes up (0.4 - 0.7 MB) and ONE kernel (csrc/depth_maps.hip) writes the maps: the
 reference's fp32 operations in the reference's order, so a point lands in the pixel it lands in on the CPU.
@@ -80,7 +80,10 @@ class HostStage:
     """Several host arrays (numpy, contiguous or made so, any dtype) -> the device through ONE pinned staging buffer and one
     asynchronous copy: they are laid into the buffer at 256-byte offsets and the device tensors returned are views of that one
     upload (uint16 arrays come back as int16 views of the same bits: torch has no uint16 views).  The buffer grows to the largest
-    sample seen and is reused once the previous copy has read it.  ``last_bytes``: the bytes of the last upload."""
+    sample seen and is reused once the previous copy has read it.  ``last_bytes``: the bytes of the last upload.
+
+    An entry of ``arrays`` may be a tuple of arrays of one dtype: they are laid BACK TO BACK, with no padding between them, and come
+    back as one flat device tensor (``sweeps.LoadPointsFromMultiSweeps``: the raw clouds as one buffer of rows)."""
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -89,7 +92,9 @@ class HostStage:
     def __call__(self, arrays):
         if self.device.type != "cuda":
             raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % self.device)
-        arrays = [np.ascontiguousarray(a) for a in arrays]
+        groups = [[np.ascontiguousarray(p) for p in a] if isinstance(a, tuple) else None for a in arrays]
+        arrays = [np.ascontiguousarray(a) if g is None else np.empty(sum(p.size for p in g), g[0].dtype if g else np.uint8)
+                  for a, g in zip(arrays, groups)]          # a group's stand-in is read for its size, dtype and shape only
         offs, at = [], 0
         for a in arrays:
             offs.append(at)
@@ -103,8 +108,10 @@ class HostStage:
         elif self._done is not None:
             self._done.synchronize()                             # the previous sample's copy has read the buffer
         host = self._stage.numpy()
-        for a, o in zip(arrays, offs):
-            host[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        for a, g, o in zip(arrays, groups, offs):
+            for p in ([a] if g is None else g):
+                host[o:o + p.nbytes] = p.reshape(-1).view(np.uint8)
+                o += p.nbytes
         dev = self._stage[:at].to(self.device, non_blocking=True)
         self._done = torch.cuda.Event()
         self._done.record()

@@ -358,7 +358,7 @@ class LoadMultiViewFrames:
         sample's ``['curr']['cams']`` dict; ``lidar2cam_dic``: 4 x 4 per camera name.  Returns ``(img_inputs, extras)``;
         ``denorm_imgs`` (index 8) has the values of ``imgs`` and SHARES its storage.
 
-        ``points``: the key-frame cloud, fp32 [P,C>=3] (a device tensor, or a numpy array / CPU tensor that is uploaded).  With it
+        ``points``: the cloud (key frame, or the merged sweeps), fp32 [P,C>=3] (a device tensor, or a numpy array / CPU tensor that is uploaded).  With it
         ``gt_depths`` (index 6) is the [N,fH,fW] LiDAR depth maps of the reference's CreateDepthFromLiDAR, made on the device
         (``depth_maps``); the camera table rides in the one small upload and is ``extras['depth_table']``.  Without it
         the slot holds the reference loader's [N,1] zeros."""

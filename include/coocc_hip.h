@@ -1189,6 +1189,41 @@ int coocc_occ_visible_rows(const float* centres, int64_t N, const float* cams, i
 int coocc_occ_cloud_aabb(const float* points, int64_t P, int point_stride, const double* transforms, uint64_t* slots, float* aabb,
                          void* stream);
 
+/* ---- the multi-sweep LiDAR cloud from the raw sweeps (co_occ_amd/sweeps.py, csrc/sweeps.hip): mmdet3d 0.17's
+ * LoadPointsFromMultiSweeps behind LoadPointsFromFile, the first step of four of the five coocc_nusc pipelines.
+ *   raw        fp32 [in_rows][load_dim] on the device: every raw cloud back to back, load_dim >= 5; may be NULL when in_rows == 0
+ *   segs       the segment table on the device, segs_host the same bytes in host memory (checked before anything is launched);
+ *              1 .. 65 records, one per output segment in output order.  A segment reads n_rows rows from in_row0 -- segments may name
+ *              the same rows (pad_empty_sweeps: sweeps_num records on the key frame) -- and out_row0 is the sum of n_rows before it
+ *   use_dim    host int32 [n_use]: the input column of every output column (1 .. 16 of them, each below load_dim)
+ *   out        fp32 [out_rows][n_use], out_rows >= the sum of n_rows
+ * Per row of a segment, in this order:
+ *   COOCC_SWEEP_FILTER     (_remove_close) the row is dropped where |x| < radius and |y| < radius: fp32, strict, on the untransformed
+ *                          coordinates; a NaN coordinate is never close
+ *   COOCC_SWEEP_TRANSFORM  xyz = (float)((double)xyz @ R^T): every product rounded in fp64, the sum (x0 R[j][0] + x1 R[j][1]) + x2 R[j][2],
+ *                          one conversion to fp32; then xyz = (float)((double)xyz + t[j]): a second conversion.  Conversions round to
+ *                          nearest even and keep denormal results; no fused multiply-add
+ *   column 4 = dt (the key frame's record has dt = 0 and no flag); columns other than 0, 1, 2, 4 are copied bit for bit.
+ * Kept rows keep their order (hard voxelisation reads it).  No segment filters: ONE launch, a thread an output row, out[0 .. total)
+ * written, count (optional) = total; no host read, capturable into a graph with no parallel branches.  Some segment filters: count is
+ * required, ws is coocc_sweeps_merge_ws(total) bytes; per-tile keep counts (wave ballot), a one-workgroup exclusive scan, a write
+ * pass -- no atomics, the same bytes from run to run -- out[0 .. *count) written, the rows past it not.  A total of 2^31 rows or more
+ * is refused (COOCC_EINVAL).  The kernels address nothing outside raw and out whatever the device table holds. */
+#define COOCC_SWEEPS_MAX_SEGS 65
+#define COOCC_SWEEPS_MAX_USE 16
+#define COOCC_SWEEP_TRANSFORM 1
+#define COOCC_SWEEP_FILTER 2
+typedef struct coocc_sweep_seg {
+  int64_t in_row0, n_rows, out_row0;
+  double R[9], t[3];
+  float dt;
+  int32_t flags;
+} coocc_sweep_seg;          /* 128 bytes */
+size_t coocc_sweeps_merge_ws(int64_t rows);
+int coocc_sweeps_merge(const float* raw, int64_t in_rows, int load_dim, const coocc_sweep_seg* segs, const coocc_sweep_seg* segs_host,
+                       int nseg, const int32_t* use_dim_host, int n_use, float radius, float* out, int64_t out_rows, int32_t* count,
+                       void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
