@@ -391,13 +391,22 @@ class DevPtr(ctypes.c_void_p):
     while later arguments of the same call are still being built."""
 
 
+def require_gpu(what, name=None):
+    """The one refusal of everything that is not on the GPU: ``what`` is a tensor (``name``: what to call it) or a device."""
+    if isinstance(what, torch.Tensor):
+        if not what.is_cuda:
+            raise CooccError("co_occ_amd ops run on the GPU only; %s a %s tensor (no CPU fallback)" % ("%s is" % name if name else "got", what.device))
+    elif torch.device(what).type != "cuda":
+        raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % (what,))
+
+
 def ptr(t, dtype=None, strided=False, offset=0):
     """Device pointer of a contiguous HIP tensor (None -> NULL), ``offset`` elements past its first.  ``strided=True`` is
     for entry points that take element strides explicitly."""
     if t is None:
         return c_void_p(0)
     if not t.is_cuda:
-        raise CooccError("co_occ_amd ops run on the GPU only; got a %s tensor (no CPU fallback)" % t.device)
+        require_gpu(t)
     if dtype is not None and t.dtype != dtype:
         raise CooccError("expected %s, got %s" % (dtype, t.dtype))
     if not strided and not t.is_contiguous():

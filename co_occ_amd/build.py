@@ -18,9 +18,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # CPU's bits; a contracted multiply-add would round once where the CPU rounds twice.
 # render_eval.hip: the uint8 comparison panels restate the reference's fp32 expression in its order and must give the CPU's bytes.
 # depth_maps.hip: the LiDAR projection restates ATen's CPU bmm of 3 x 3 matrices -- every product rounded, sums left to right -- so the
-# pixel a point rounds to is the CPU's; a contracted chain moves one written pixel in six.
+# pixel a point rounds to is the CPU's; a contracted chain moves one written pixel in six.  The chain itself is in
+# lidar_project.h: a header is compiled with the flags of the file that includes it, so both files that include it stay listed here.
 # occ_gt.hip: the occupancy ground truth is integers decided by floats -- a voxel index from a float64 centre rounded to fp32,
-# rotated in fp32 and divided in float64, a pixel and d*10 from depth_maps.hip's projection chain, a box from two float64 transforms --
+# rotated in fp32 and divided in float64, a pixel and d*10 from lidar_project.h's projection chain, a box from two float64 transforms --
 # and each is rounded where numpy and ATen's CPU code round it; a contracted multiply-add moves a centre across a voxel border
 # (DESIGN.md 16).
 # sweeps.hip: the sweep transform restates numpy's float64 xyz @ R.T and + t with a rounding to fp32 after each -- every product

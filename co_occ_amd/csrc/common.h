@@ -41,6 +41,9 @@ int coocc_set_error(int code, const char* fmt, ...);
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline unsigned cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+// Workspace carving (host): every array of a workspace starts on a 256-byte boundary, counted from the aligned base.
+static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+static inline char* ws_base256(void* ws) { return (char*)al256((uintptr_t)ws); }
 
 // Mean and rstd (two-pass, biased variance) of the cpg channels one thread of the row-wise GroupNorm kernels walks (k_groupnorm_rows,
 // k_groupnorm_rows_bwd).  Acc = float: the sequential fp32 sums of the 4-channel groups of the fine branch.  Groups wider than

@@ -200,7 +200,7 @@ extern "C" int coocc_depth_bce(const float* prob, const int32_t* labels, int BN,
   const size_t need = coocc_depth_bce_ws(P, D);
   COOCC_CHECK_ARG(ws_bytes >= need, "depth_bce: workspace too small (%zu < %zu bytes)", ws_bytes, need);
   const int nblk = db_blocks(P), nsl = db_slices(D);
-  double* part = (double*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* part = (double*)ws_base256(ws);
   double* cnt = part + (size_t)nblk * nsl;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(k_depth_bce, dim3(nblk, nsl), dim3(256), 0, s, prob, labels, (long long)P, D, h * w, part, cnt);

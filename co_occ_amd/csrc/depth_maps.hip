@@ -2,11 +2,8 @@
 // (P/datasets/pipelines/lidar2depth.py:19-41, 63-85) -- the key-frame cloud projected into every camera and the nearest depth per
 // pixel kept -- without the N x H x W map ever being made on the host.
 //
-// Per point p and camera (inv_rot, tran, intrin, post_rot 2x2, post_tran), in the reference's fp32 operations and their order:
-//   q = p - tran;  c = inv_rot @ q;  k = intrin @ c;  d = k[2];  uv = k[:2] / d;  uv = post_rot @ uv + post_tran
-// ATen's CPU bmm of these small matrices rounds every product and adds them left to right, so a row is (a0*x0 + a1*x1) + a2*x2 with
-// five roundings: this file is compiled with -ffp-contract=off (build.FILE_FLAGS) and the division is IEEE (__fdiv_rn).  A fused
-// chain gives other u, v or d for six pairs in ten and changes one written pixel in six.
+// The projection (csrc/lidar_project.h, shared with occ_gt.hip) is the reference's fp32 operations in their order: this file is compiled
+// with -ffp-contract=off (build.FILE_FLAGS).  A fused chain gives other u, v or d for six pairs in ten and changes one written pixel in six.
 // A pair is valid where u >= 0 & v >= 0 & u <= W-1 & v <= H-1 & d > 0 on the unrounded values (a NaN fails every test); its pixel
 // is (rint(v), rint(u)), half to even.
 //
@@ -19,8 +16,7 @@
 // k_points_to_depth_maps: a thread owns one point and walks the cameras; a camera record is addressed by kernel arguments and the
 // loop counter alone, so its 27 floats are scalar loads.  ~35 k points x 6 cameras against a 4 - 34 MB fill: latency-bound.
 #include "common.h"
-
-constexpr int DM_CAM_FLOATS = 28;          // inv_rot[9] tran[3] intrin[9] post_rot 2x2 [4] post_tran[2] pad
+#include "lidar_project.h"
 
 __global__ __launch_bounds__(256) COOCC_SCALAR_FP32 void k_points_to_depth_maps(const float* __restrict__ points, long long P, int point_stride,
                                                                                 const float* __restrict__ cams, int N, int H, int W,
@@ -31,17 +27,8 @@ __global__ __launch_bounds__(256) COOCC_SCALAR_FP32 void k_points_to_depth_maps(
   const float x = p[0], y = p[1], z = p[2];
   const float umax = (float)(W - 1), vmax = (float)(H - 1);
   for (int cam = 0; cam < N; ++cam) {
-    const float* C = cams + (size_t)cam * DM_CAM_FLOATS;
-    const float q0 = x - C[9], q1 = y - C[10], q2 = z - C[11];
-    const float c0 = (C[0] * q0 + C[1] * q1) + C[2] * q2;
-    const float c1 = (C[3] * q0 + C[4] * q1) + C[5] * q2;
-    const float c2 = (C[6] * q0 + C[7] * q1) + C[8] * q2;
-    const float k0 = (C[12] * c0 + C[13] * c1) + C[14] * c2;
-    const float k1 = (C[15] * c0 + C[16] * c1) + C[17] * c2;
-    const float d = (C[18] * c0 + C[19] * c1) + C[20] * c2;
-    const float u0 = __fdiv_rn(k0, d), v0 = __fdiv_rn(k1, d);
-    const float u = (C[21] * u0 + C[22] * v0) + C[25];
-    const float v = (C[23] * u0 + C[24] * v0) + C[26];
+    float u, v, d;
+    lidar_project(cams + (size_t)cam * LIDAR_CAM_FLOATS, x, y, z, u, v, d);
     if (!(u >= 0.f && v >= 0.f && u <= umax && v <= vmax && d > 0.f)) continue;
     const int px = (int)rintf(u), py = (int)rintf(v);          // 0 .. W-1, 0 .. H-1 by the test above
     unsigned int* cell = maps + ((size_t)cam * H + py) * W + px;

@@ -74,8 +74,6 @@ __global__ void k_vox_count(const int32_t* __restrict__ rank, const int32_t* __r
   }
 }
 
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 extern "C" size_t coocc_voxelize_ws(int n) {
   if (n <= 0) return 256;
   size_t tmp = 0, tmp2 = 0, tmp3 = 0;
@@ -104,7 +102,7 @@ extern "C" int coocc_voxelize_hard(const float* points, int n, int F, const floa
   COOCC_HIP(hipMemsetAsync(count, 0, sizeof(int32_t), s));
   if (n == 0) return COOCC_OK;
   if (!ws || ws_bytes < coocc_voxelize_ws(n)) return coocc_set_error(COOCC_ENOMEM, "voxelize_hard: workspace too small");
-  char* c = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* c = ws_base256(ws);
   const size_t a = al256(sizeof(uint32_t) * (size_t)n);
   uint32_t* k_in = (uint32_t*)c; c += a;
   uint32_t* k_out = (uint32_t*)c; c += a;

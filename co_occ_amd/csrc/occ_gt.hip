@@ -13,8 +13,8 @@
 //   vote    k_vote_keys + rocprim::radix_sort_keys + k_vote_runs: keys voxel * 256 + label sorted, then the thread on a voxel's first
 //           key walks its label runs in ascending label: count modulo 65 536 (the reference's uint16 counter), strictly greater
 //           replaces -- np.argmax, the lowest label among the maxima.  No atomics on the volume; independent of the row order.
-//   masks   k_visible_min + k_visible_flag: the projection chain of depth_maps.hip; a pixel keeps the lexicographic minimum of
-//           (d*10 truncated, row) below 2048 with a 64-bit atomicMin -- the reference's sequential z-buffer, whose strict `<` lets the
+//   masks   k_visible_min + k_visible_flag: lidar_project (csrc/lidar_project.h), the chain depth_maps.hip calls; a pixel keeps the lexicographic
+//           minimum of (d*10 truncated, row) below 2048 with a 64-bit atomicMin -- the reference's sequential z-buffer, whose strict `<` lets the
 //           lowest row win among equals -- and a row is visible if it is the pixel's winner in any camera.
 //   aabb    k_cloud_aabb + k_aabb_final: the two rigid float64 transforms left to right, min / max on order-preserving 64-bit keys,
 //           one rounding to fp32 at the end; a NaN takes the all-ones key in both slots and comes out as NaN, as numpy's min / max.
@@ -25,17 +25,15 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "lidar_project.h"
 
 namespace {
 
-constexpr int OG_CAM_FLOATS = 28;          // the camera record of depth_maps.hip
 constexpr unsigned OG_DROPPED = 0xFFFFFFFFu;
 
 struct OgGrid { double lo[3], hi[3], vs[3]; int g[3]; };
 struct OgMat { float m[9]; int on; };
 struct OgXf { double r1[9], t1[3], r2[9], t2[3]; };
-
-static inline size_t og_al256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------- form A
 __global__ __launch_bounds__(256) void k_scatter_win(const uint16_t* __restrict__ rows, long long N, int G0, int G1, int G2, int use_semantic,
@@ -185,16 +183,8 @@ __global__ __launch_bounds__(256) void k_vote_runs(const unsigned int* __restric
 // ---------------------------------------------------------------- the camera visibility of the centres
 __device__ __forceinline__ bool og_project(const float* __restrict__ C, float x, float y, float z, int H, int W, int& px, int& py,
                                            int& d10) {
-  const float q0 = x - C[9], q1 = y - C[10], q2 = z - C[11];
-  const float c0 = (C[0] * q0 + C[1] * q1) + C[2] * q2;
-  const float c1 = (C[3] * q0 + C[4] * q1) + C[5] * q2;
-  const float c2 = (C[6] * q0 + C[7] * q1) + C[8] * q2;
-  const float k0 = (C[12] * c0 + C[13] * c1) + C[14] * c2;
-  const float k1 = (C[15] * c0 + C[16] * c1) + C[17] * c2;
-  const float d = (C[18] * c0 + C[19] * c1) + C[20] * c2;
-  const float u0 = __fdiv_rn(k0, d), v0 = __fdiv_rn(k1, d);
-  const float u = (C[21] * u0 + C[22] * v0) + C[25];
-  const float v = (C[23] * u0 + C[24] * v0) + C[26];
+  float u, v, d;
+  lidar_project(C, x, y, z, u, v, d);
   if (!(u >= 0.f && u < (float)W && v >= 0.f && v < (float)H && d >= 0.f)) return false;
   const float t = d * 10.f;
   if (!(t < 2048.f)) return false;          // never below the canvas's 2048; covers d*10 >= 32 768, where the int16 cast is undefined
@@ -210,7 +200,7 @@ __global__ __launch_bounds__(256) COOCC_SCALAR_FP32 void k_visible_min(const flo
   const float x = centres[i * 3], y = centres[i * 3 + 1], z = centres[i * 3 + 2];
   for (int cam = 0; cam < ncam; ++cam) {
     int px, py, d10;
-    if (!og_project(cams + (size_t)cam * OG_CAM_FLOATS, x, y, z, H, W, px, py, d10)) continue;
+    if (!og_project(cams + (size_t)cam * LIDAR_CAM_FLOATS, x, y, z, H, W, px, py, d10)) continue;
     atomicMin(canvas + ((size_t)cam * H + py) * W + px, ((unsigned long long)d10 << 32) | (unsigned long long)i);
   }
 }
@@ -225,7 +215,7 @@ __global__ __launch_bounds__(256) COOCC_SCALAR_FP32 void k_visible_flag(const fl
   uint8_t seen = 0;
   for (int cam = 0; cam < ncam; ++cam) {
     int px, py, d10;
-    if (!og_project(cams + (size_t)cam * OG_CAM_FLOATS, x, y, z, H, W, px, py, d10)) continue;
+    if (!og_project(cams + (size_t)cam * LIDAR_CAM_FLOATS, x, y, z, H, W, px, py, d10)) continue;
     if (canvas[((size_t)cam * H + py) * W + px] == (((unsigned long long)d10 << 32) | (unsigned long long)i)) seen = 1;
   }
   flags[i] = seen;
@@ -347,7 +337,7 @@ extern "C" size_t coocc_occ_vote_ws(int64_t N) {
   if (N <= 0 || N >= ((int64_t)1 << 31)) return 256;
   size_t tmp = 0;
   (void)rocprim::radix_sort_keys(nullptr, tmp, (unsigned int*)nullptr, (unsigned int*)nullptr, (size_t)N, 0, 32, (hipStream_t)0);
-  return 256 + 2 * og_al256(4 * (size_t)N) + og_al256(tmp) + 256;
+  return 256 + 2 * al256(4 * (size_t)N) + al256(tmp) + 256;
 }
 
 extern "C" int coocc_occ_vote_labels(const int32_t* vox, const uint8_t* labels, int64_t N, int64_t V, int fill, int post_empty, uint8_t* vol,
@@ -362,11 +352,11 @@ extern "C" int coocc_occ_vote_labels(const int32_t* vox, const uint8_t* labels, 
   if (N == 0) return COOCC_OK;
   const size_t need = coocc_occ_vote_ws(N);
   if (ws_bytes < need) return coocc_set_error(COOCC_ENOMEM, "occ_vote_labels: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-  char* b = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* b = ws_base256(ws);
   unsigned int* dropped = (unsigned int*)b;
   unsigned int* k_in = (unsigned int*)(b + 256);
-  unsigned int* k_out = (unsigned int*)(b + 256 + og_al256(4 * (size_t)N));
-  char* tmp = b + 256 + 2 * og_al256(4 * (size_t)N);
+  unsigned int* k_out = (unsigned int*)(b + 256 + al256(4 * (size_t)N));
+  char* tmp = b + 256 + 2 * al256(4 * (size_t)N);
   size_t tmp_bytes = 0;
   (void)rocprim::radix_sort_keys(nullptr, tmp_bytes, (unsigned int*)nullptr, (unsigned int*)nullptr, (size_t)N, 0, 32, (hipStream_t)0);
   COOCC_HIP(hipMemsetAsync(dropped, 0, 256, s));

@@ -30,7 +30,6 @@ constexpr int OL_MAXBLK = 256;               // pass-1 blocks (grid-stride over 
 constexpr int OL_D = OL_NPART;
 static_assert(OL_D + 8 + 2 * OL_MAXC == COOCC_OCC_LOSS_STATS, "statistics block layout");
 
-static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // -log(x) clamped at 100 as losses._bce_to_one: value 100 and ZERO gradient at or below 1e-43
 __device__ __forceinline__ double bce1(double x) { return x > 1e-43 ? -log(x) : 100.0; }
@@ -427,7 +426,7 @@ extern "C" int coocc_occ_loss_fwd(const float* logits, int64_t P, int C, int ld,
                   "occ_loss_fwd: the coordinate form needs row_labels and the volume's extents");
   OlLayout L = ol_layout(P, C);
   if (ws_bytes < L.total) return coocc_set_error(COOCC_ENOMEM, "occ_loss_fwd: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-  char* b = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* b = ws_base256(ws);
   double* part = (double*)(b + L.part);
   unsigned long long *k_in = (unsigned long long*)(b + L.keys_in), *k_out = (unsigned long long*)(b + L.keys_out);
   unsigned *v_in = (unsigned*)(b + L.vals_in), *v_out = (unsigned*)(b + L.vals_out);

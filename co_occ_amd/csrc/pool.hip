@@ -1061,14 +1061,12 @@ __global__ __launch_bounds__(256) void k_pool_sum_seg(const float* __restrict__ 
 // r101 (0.325 -> 0.410 ms: the long voxels' serial chains, 233 us, are the launch and they run slower next to a denser short
 // kernel); a rank sort instead of the bitonic network and 128 rows in flight made the long path slower still (233 -> 303 us).
 // profiles/r4_pool_experiments.txt.)
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // workspace: keys[npts] | ids[npts] | slot[npts] | count[nvox+1] | nlong [64] (one memset clears these two when the caller does
 // not vouch for them) | start[nvox+1] | lstart[nvox+1] | long_list[nvox] | tops[nvox / 1024 + 2] | wts[npts] | wcsr[npts] | rowmax[npts / D <= npts] (segment form)
 extern "C" size_t coocc_voxel_pool_ws(int npts, int nvox) {
   if (npts <= 0 || nvox <= 0) return 0;
-  return 6 * align256(sizeof(uint32_t) * (size_t)npts) + 4 * align256(sizeof(int32_t) * ((size_t)nvox + 1)) + 256 +
-         align256(sizeof(int32_t) * ((size_t)nvox / 1024 + 2)) + 8192 + 256;
+  return 6 * al256(sizeof(uint32_t) * (size_t)npts) + 4 * al256(sizeof(int32_t) * ((size_t)nvox + 1)) + 256 +
+         al256(sizeof(int32_t) * ((size_t)nvox / 1024 + 2)) + 8192 + 256;
 }
 
 struct PoolWs { uint32_t *keys, *ids; int32_t *slot, *count, *nlong, *start, *lstart, *long_list, *tops; float *wts, *wcsr, *rowmax; size_t zero_bytes; };
@@ -1076,13 +1074,13 @@ struct PoolWs { uint32_t *keys, *ids; int32_t *slot, *count, *nlong, *start, *ls
 static int carve(void* ws, size_t ws_bytes, int npts, int nvox, PoolWs* p) {
   size_t need = coocc_voxel_pool_ws(npts, nvox);
   if (!ws || ws_bytes < need) return coocc_set_error(COOCC_ENOMEM, "voxel_pool: workspace %zu < %zu bytes", ws_bytes, need);
-  char* c = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  size_t a = align256(sizeof(uint32_t) * (size_t)npts), v = align256(sizeof(int32_t) * ((size_t)nvox + 1));
+  char* c = ws_base256(ws);
+  size_t a = al256(sizeof(uint32_t) * (size_t)npts), v = al256(sizeof(int32_t) * ((size_t)nvox + 1));
   p->keys = (uint32_t*)c; c += a; p->ids = (uint32_t*)c; c += a; p->slot = (int32_t*)c; c += a;
   p->count = (int32_t*)c; c += v; p->nlong = (int32_t*)c; c += 256;
   p->zero_bytes = v + 256;
   p->start = (int32_t*)c; c += v; p->lstart = (int32_t*)c; c += v; p->long_list = (int32_t*)c; c += v; p->tops = (int32_t*)c;
-  c += align256(sizeof(int32_t) * ((size_t)nvox / 1024 + 2)) + 8192;
+  c += al256(sizeof(int32_t) * ((size_t)nvox / 1024 + 2)) + 8192;
   p->wts = (float*)c; c += a;
   p->wcsr = (float*)c; c += a;
   p->rowmax = (float*)c;

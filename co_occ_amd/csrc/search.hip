@@ -20,8 +20,6 @@ __global__ __launch_bounds__(256) void k_gather_xyz(const float* __restrict__ xy
   out[i * 3 + 0] = xyz[s * 3 + 0]; out[i * 3 + 1] = xyz[s * 3 + 1]; out[i * 3 + 2] = xyz[s * 3 + 2];
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct SearchWs {
   uint8_t* flags;        // [2][V]
   int32_t* cws;          // [2][V/1024 + 2]
@@ -42,7 +40,7 @@ struct SearchWs {
 static SearchWs carve(char* base, int V, int K, int fps_num, int max_cluster, int X, int Y, int Z) {
   SearchWs w;
   size_t o = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
+  auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += al256(bytes); return p; };
   w.flags = (uint8_t*)take((size_t)2 * V);
   w.cws = (int32_t*)take((size_t)2 * (V / 1024 + 2) * 4);
   w.xyz = (float*)take((size_t)2 * V * 3 * 4);

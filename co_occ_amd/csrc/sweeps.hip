@@ -164,12 +164,11 @@ __global__ __launch_bounds__(SW_TILE) COOCC_SCALAR_FP32 void k_sweeps_merge(cons
   }
 }
 
-static size_t sw_al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 extern "C" size_t coocc_sweeps_merge_ws(int64_t rows) {
   if (rows <= 0) return 256;
   const size_t ntiles = ((size_t)rows + SW_TILE - 1) / SW_TILE;
-  return 2 * sw_al256(sizeof(int32_t) * ntiles) + 256;
+  return 2 * al256(sizeof(int32_t) * ntiles) + 256;
 }
 
 extern "C" int coocc_sweeps_merge(const float* raw, int64_t in_rows, int load_dim, const coocc_sweep_seg* segs,
@@ -220,9 +219,9 @@ extern "C" int coocc_sweeps_merge(const float* raw, int64_t in_rows, int load_di
     return COOCC_OK;
   }
   if (!ws || ws_bytes < coocc_sweeps_merge_ws(total)) return coocc_set_error(COOCC_ENOMEM, "sweeps_merge: workspace too small");
-  char* c = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  char* c = ws_base256(ws);
   int32_t* tile_count = (int32_t*)c;
-  int32_t* tile_off = (int32_t*)(c + sw_al256(sizeof(int32_t) * (size_t)ntiles));
+  int32_t* tile_off = (int32_t*)(c + al256(sizeof(int32_t) * (size_t)ntiles));
   hipLaunchKernelGGL(k_sweeps_count, dim3(ntiles), dim3(SW_TILE), 0, st, rawu, (long long)in_rows, load_dim, segs, nseg, total, radius, tile_count);
   COOCC_LAUNCH_CHECK("k_sweeps_count");
   hipLaunchKernelGGL(k_sweeps_scan, dim3(1), dim3(SW_TILE), 0, st, tile_count, (int)ntiles, tile_off, count);

@@ -21,12 +21,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CooccError, ptr
+from ._lib import CooccError, ptr, require_gpu
+from .staging import HostStage, PointStage, device_points, device_tensor, pinned_upload
 
 PRECISION_BITS = 22          # Pillow's 32 - 8 - 2
 MAX_TAPS = 33                # csrc/image_inputs.hip II_KMAX: bicubic (support 2) at a downscale ratio of 8
 MAX_RATIO = 8
 CAM_INTS = 12                # per-camera header of coocc_frames_to_imgs
+CAM_FLOATS = 28              # csrc/lidar_project.h LIDAR_CAM_FLOATS: inv_rot[9] tran[3] intrin[9] post_rot 2x2 [4] post_tran[2] pad
 
 
 # ------------------------------------------------------------------ Pillow's coefficient tables
@@ -170,6 +172,65 @@ def calibration(cam_data, lidar2cam):
     return dict(intrin=intrin, cam2world=cam2world, sensor2lidar=sensor2lidar, rot=sensor2lidar[:3, :3], tran=sensor2lidar[:3, 3])
 
 
+def choose_cams(data_config, is_train, rng=np.random):
+    """The cameras of a sample: ``Ncams`` drawn from ``cams`` without replacement in training, else all of them."""
+    if is_train and data_config['Ncams'] < len(data_config['cams']):
+        return rng.choice(data_config['cams'], data_config['Ncams'], replace=False)
+    return data_config['cams']
+
+
+def require_calibration(cam_names, cam_infos, lidar2cam_dic):
+    missing = [c for c in cam_names if c not in cam_infos or c not in lidar2cam_dic]
+    if missing:
+        raise ValueError("no calibration for cameras %s" % missing)
+
+
+# ------------------------------------------------------------------ the LiDAR depth slot (DESIGN.md 15; the loaders are in depth_maps)
+def camera_table(rots, trans, intrins, post_rots, post_trans):
+    """The ``[N,28]`` host table of ``coocc_points_to_depth_maps`` from CPU fp32 tensors ``rots`` [N,3,3], ``trans`` [N,3],
+    ``intrins`` [N,3,3], ``post_rots`` [N,3,3] (or [N,2,2]) and ``post_trans`` [N,3] (or [N,2]).  ``rots.inverse()`` is taken here, on
+    the CPU and batched, as the reference calls it."""
+    ts = dict(rots=rots, trans=trans, intrins=intrins, post_rots=post_rots, post_trans=post_trans)
+    for k, t in ts.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("camera_table: %s must be a float32 tensor, got %s" % (k, getattr(t, "dtype", type(t).__name__)))
+        if t.is_cuda:
+            raise ValueError("camera_table: %s is on %s; the table is made on the host (rots.inverse() with the reference's bits)" % (k, t.device))
+    if intrins.dim() == 3 and tuple(intrins.shape[-2:]) == (4, 4):
+        raise NotImplementedError("camera_table: 4 x 4 intrinsics (the reference's KITTI form) are not restated; nuScenes' are 3 x 3")
+    N = rots.shape[0] if rots.dim() == 3 else -1
+    if N < 1 or tuple(rots.shape) != (N, 3, 3) or tuple(trans.shape) != (N, 3) or tuple(intrins.shape) != (N, 3, 3):
+        raise ValueError("camera_table: rots [N,3,3], trans [N,3], intrins [N,3,3]; got %s, %s, %s"
+                         % (tuple(rots.shape), tuple(trans.shape), tuple(intrins.shape)))
+    if tuple(post_rots.shape) not in ((N, 3, 3), (N, 2, 2)) or tuple(post_trans.shape) not in ((N, 3), (N, 2)):
+        raise ValueError("camera_table: post_rots [N,3,3] and post_trans [N,3] for N = %d; got %s, %s"
+                         % (N, tuple(post_rots.shape), tuple(post_trans.shape)))
+    return torch.cat([rots.inverse().reshape(N, 9), trans, intrins.reshape(N, 9), post_rots[:, :2, :2].reshape(N, 4),
+                      post_trans[:, :2], torch.zeros(N, 1)], 1).contiguous()
+
+
+def points_to_depth_maps(points, table, size, out=None):
+    """fp32 ``[N,H,W]`` depth maps of ``points`` (device fp32 ``[P,C>=3]``, x y z first; made contiguous when it is not) for the cameras
+    of ``table`` (device fp32 ``[N,28]``, ``camera_table``), ``size = (H, W)``.  Runs on the current stream: a zero fill and one launch,
+    no host read; capturable into a graph with no parallel branches.  ``out``: written in place (entirely) when given."""
+    points, table = device_points(points), device_tensor("table", table, torch.float32, CAM_FLOATS)
+    if table.shape[0] < 1:
+        raise ValueError("table must be [N >= 1, %d], got %s" % (CAM_FLOATS, tuple(table.shape)))
+    if table.device != points.device:
+        raise CooccError("points on %s, table on %s" % (points.device, table.device))
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError("size must be (H >= 1, W >= 1), got %s" % ((H, W),))
+    N = table.shape[0]
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.float32, device=points.device)
+    elif tuple(out.shape) != (N, H, W):
+        raise ValueError("out must be [%d, %d, %d], got %s" % (N, H, W, tuple(out.shape)))
+    _lib.call("coocc_points_to_depth_maps", ptr(points, torch.float32), points.shape[0], points.shape[1], ptr(table, torch.float32), N, H, W,
+              ptr(out, torch.float32))
+    return out
+
+
 # ------------------------------------------------------------------ the plan: per-camera parameters and tables, resident on the device
 class ResizePlan:
     """What ``coocc_frames_to_imgs`` needs beside the frames: per camera ``resize_dims`` (newW, newH), ``crop`` (x0, y0, x1, y1) and
@@ -228,14 +289,12 @@ class ResizePlan:
     def resident(self, device):
         """(params, tables, pinned host copy) on ``device``; the first call per device uploads, on the current stream."""
         device = torch.device(device)
-        if device.type != "cuda":
-            raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % device)
+        require_gpu(device)
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         got = self._dev.get(device)
         if got is None:
-            pinned = torch.from_numpy(self.host.copy()).pin_memory()
-            dev = pinned.to(device, non_blocking=True)
+            dev, pinned = pinned_upload(torch.from_numpy(self.host), device)
             n = self.N * CAM_INTS
             got = self._dev[device] = (dev[:n], dev[n:], pinned)
         return got
@@ -275,8 +334,7 @@ def frames_to_imgs(frames, plan, out=None, canvas=None):
     if (Hs, Ws) != (plan.Hs, plan.Ws):
         raise ValueError("frames are %d x %d, the plan was made for %d x %d" % (Hs, Ws, plan.Hs, plan.Ws))
     first = frames if isinstance(frames, torch.Tensor) else frames[0]
-    if not first.is_cuda:
-        raise CooccError("co_occ_amd ops run on the GPU only; got a %s tensor (no CPU fallback)" % first.device)
+    require_gpu(first)
     device = first.device
     params, tables, pinned = plan.resident(device)
     if out is None:
@@ -292,7 +350,7 @@ def frames_to_imgs(frames, plan, out=None, canvas=None):
             ptr(f, torch.uint8)                                  # device, dtype, contiguity
             if f.device != device:
                 raise CooccError("frames on different devices: %s and %s" % (device, f.device))
-        keep = torch.tensor([f.data_ptr() for f in frames], dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        keep = pinned_upload(torch.tensor([f.data_ptr() for f in frames], dtype=torch.int64), device)[0]
         fptr, pptr = ptr(None), ptr(keep)
     _lib.call("coocc_frames_to_imgs", fptr, pptr, N, Hs, Ws, ptr(params, torch.int32), ctypes.c_void_p(pinned.data_ptr()),
               ptr(tables, torch.int32), plan.table_ints, plan.fH, plan.fW, ptr(out, torch.float32), ptr(canvas, torch.uint8))
@@ -312,15 +370,11 @@ class LoadMultiViewFrames:
     def __init__(self, data_config, is_train=False, device="cuda", rng=np.random):
         self.data_config, self.is_train, self.device, self.rng = data_config, is_train, torch.device(device), rng
         self._plans = collections.OrderedDict()
-        self._stage = None
-        self._stage_done = None
+        self._stage, self._small_stage = HostStage(self.device, threaded_fill=True), HostStage(self.device)          # frames | matrices
         self._point_stage = None
 
     def choose_cams(self):
-        cfg = self.data_config
-        if self.is_train and cfg['Ncams'] < len(cfg['cams']):
-            return self.rng.choice(cfg['cams'], cfg['Ncams'], replace=False)
-        return cfg['cams']
+        return choose_cams(self.data_config, self.is_train, self.rng)
 
     def _plan(self, Hs, Ws, cams):
         fH, fW = self.data_config['input_size']
@@ -335,22 +389,13 @@ class LoadMultiViewFrames:
         return plan
 
     def _upload(self, frames):
-        """Host frames (numpy arrays or CPU tensors, uint8 [Hs,Ws,3]) -> one device tensor [N,Hs,Ws,3]: the bytes go through one
-        pinned staging buffer and one asynchronous copy."""
+        """Host frames (numpy arrays or CPU tensors, uint8 [Hs,Ws,3]) -> one device tensor [N,Hs,Ws,3]: the bytes go back to back
+        through one pinned staging buffer and one asynchronous copy (a ``HostStage`` group)."""
         ts = [torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f for f in frames]
         ts, N, Hs, Ws = _check_frames(ts)
         if all(t.is_cuda for t in ts):
             return ts
-        if self._stage is None or tuple(self._stage.shape) != (N, Hs, Ws, 3):
-            self._stage = torch.empty((N, Hs, Ws, 3), dtype=torch.uint8).pin_memory()
-        elif self._stage_done is not None:
-            self._stage_done.synchronize()                       # the previous sample's copy has read the buffer
-        for i, t in enumerate(ts):
-            self._stage[i].copy_(t)
-        dev = self._stage.to(self.device, non_blocking=True)
-        self._stage_done = torch.cuda.Event()
-        self._stage_done.record()
-        return dev
+        return self._stage([tuple(t.numpy() for t in ts)])[0].view(N, Hs, Ws, 3)
 
     def __call__(self, frames, cam_infos, lidar2cam_dic, flip=None, scale=None, points=None):
         """``frames``: the decoded frames of the chosen cameras in the order of ``cam_names`` (a sequence, a [N,Hs,Ws,3] tensor, or a
@@ -368,9 +413,7 @@ class LoadMultiViewFrames:
         n_frames = frames.shape[0] if isinstance(frames, torch.Tensor) and frames.dim() == 4 else len(frames)
         if n_frames != len(cam_names):
             raise ValueError("%d frames for the %d cameras %s" % (n_frames, len(cam_names), list(cam_names)))
-        missing = [c for c in cam_names if c not in cam_infos or c not in lidar2cam_dic]
-        if missing:
-            raise ValueError("no calibration for cameras %s" % missing)
+        require_calibration(cam_names, cam_infos, lidar2cam_dic)
         if isinstance(frames, torch.Tensor):
             dev_frames = _check_frames(frames)[0]
             if not dev_frames.is_cuda:
@@ -400,20 +443,14 @@ class LoadMultiViewFrames:
         # the small tensors: stacked on the host, one upload, views of it
         stacked = {k: torch.stack(v) for k, v in cols.items()}
         if points is not None:
-            from . import depth_maps
-            stacked["depth_table"] = depth_maps.camera_table(*[stacked[k] for k in ("rots", "trans", "intrins", "post_rots", "post_trans")])
-        flat = torch.cat([t.reshape(-1) for t in stacked.values()])
-        flat = (flat.pin_memory() if self.device.type == "cuda" else flat).to(self.device, non_blocking=True)
-        m, at = {}, 0
-        for k, t in stacked.items():
-            m[k] = flat[at:at + t.numel()].view(t.shape)
-            at += t.numel()
+            stacked["depth_table"] = camera_table(*[stacked[k] for k in ("rots", "trans", "intrins", "post_rots", "post_trans")])
+        m = self._small_stage.named(stacked)
         extras = dict(canvas=canvas, cam_names=cam_names, params=drawn, plan=plan)
         gt_depths = m["gt_depths"]
         if points is not None:
             if self._point_stage is None:
-                self._point_stage = depth_maps.PointStage(self.device)
-            gt_depths = depth_maps.points_to_depth_maps(self._point_stage(points), m["depth_table"], (plan.fH, plan.fW))
+                self._point_stage = PointStage(self.device)
+            gt_depths = points_to_depth_maps(self._point_stage(points), m["depth_table"], (plan.fH, plan.fW))
             extras["depth_table"] = m["depth_table"]
         img_inputs = (imgs, m["rots"], m["trans"], m["intrins"], m["post_rots"], m["post_trans"], gt_depths, m["sensor2sensors"],
                       imgs, m["intrin_nerf"], m["c2ws"], imgs.shape[-2:])

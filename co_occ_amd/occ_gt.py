@@ -24,7 +24,8 @@ import torch
 
 from . import _lib, core, depth_maps
 from . import image_inputs as II
-from ._lib import CooccError, ptr
+from ._lib import ptr
+from .staging import HostStage, check_points, device_points, device_tensor
 
 MAX_VOXELS = 1 << 24         # keys voxel * 256 + label in 32 bits
 
@@ -72,18 +73,6 @@ def _range(pc_range, grid):
     return r, (r[3:] - r[:3]) / np.asarray(grid)          # voxel_size in float64, as the reference makes it
 
 
-def _dev(name, t, dtype, cols=None, dim=2):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s must be a tensor, got %s" % (name, type(t).__name__))
-    if not t.is_cuda:
-        raise CooccError("co_occ_amd ops run on the GPU only; %s is a %s tensor (no CPU fallback)" % (name, t.device))
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if t.dim() != dim or (cols is not None and t.shape[-1] != cols):
-        raise ValueError("%s must have %d dimensions%s, got %s" % (name, dim, "" if cols is None else " and %d columns" % cols, tuple(t.shape)))
-    return t.contiguous()
-
-
 def _doubles(vals):
     v = [float(x) for x in vals]
     return (ctypes.c_double * len(v))(*v)
@@ -127,9 +116,6 @@ def pack_rows(occ, label_col=3, grid_size=None, to_float32=False):
     return out
 
 
-HostStage = depth_maps.HostStage          # the one pinned staging buffer of a sample, shared with depth_maps.PointStage
-
-
 SCRATCH_KINDS = ("occ_gt_win", "occ_gt_vote", "occ_gt_canvas", "occ_gt_aabb")
 
 
@@ -147,7 +133,7 @@ def scatter_labels(rows, grid_size, use_semantic=True, out=None):
     ``pack_rows``' uint16 bits), 0 elsewhere; the last row of a voxel wins.  ``use_semantic``: label 0 is written as 255; without it
     rows of label 0 are dropped and the rest write 1."""
     g = _grid(grid_size)
-    rows = _dev("rows", rows, torch.int16, 4)
+    rows = device_tensor("rows", rows, torch.int16, 4)
     if rows.shape[0] >= (1 << 24) - 1:
         raise ValueError("scatter_labels takes fewer than 2^24 - 1 rows, got %d" % rows.shape[0])
     V = g[0] * g[1] * g[2]
@@ -167,7 +153,7 @@ def rows_to_voxels(rows, grid_size, pc_range, bda_rot=None, centres=True):
     fp32 centres the camera mask projects."""
     g = _grid(grid_size)
     r, vs = _range(pc_range, g)
-    rows = _dev("rows", rows, torch.int16, 4)
+    rows = device_tensor("rows", rows, torch.int16, 4)
     N = rows.shape[0]
     vox = torch.empty(N, dtype=torch.int32, device=rows.device)
     labels = torch.empty(N, dtype=torch.uint8, device=rows.device)
@@ -186,11 +172,7 @@ def points_to_voxels(points, mode, grid_size=None, pc_range=None, bda_rot=None, 
     m = {"none": 0, "annotation": 1, "lidar_mask": 2}.get(mode)
     if m is None:
         raise ValueError("mode must be 'none', 'annotation' or 'lidar_mask', got %r" % (mode,))
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        _dev("points", points, torch.float32)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3:
-        raise ValueError("points must be float32 [P, C >= 3], got %s %s" % (points.dtype, tuple(points.shape)))
-    points = points.contiguous()
+    points = device_points(points)
     P, dev = points.shape[0], points.device
     g, grid = (1, 1, 1), None
     if m:
@@ -198,7 +180,7 @@ def points_to_voxels(points, mode, grid_size=None, pc_range=None, bda_rot=None, 
         r, vs = _range(pc_range, g)
         grid = _doubles(list(r[:3]) + list(r[3:] - 1e-5 if m == 1 else r[3:]) + list(vs))
     if lidarseg is not None:
-        lidarseg, table = _dev("lidarseg", lidarseg, torch.uint8, dim=1), _dev("table", table, torch.uint8, 256, dim=1)
+        lidarseg, table = device_tensor("lidarseg", lidarseg, torch.uint8, dim=1), device_tensor("table", table, torch.uint8, 256, dim=1)
         if lidarseg.shape[0] != P:
             raise ValueError("%d lidarseg bytes for %d points" % (lidarseg.shape[0], P))
     if m == 0 and not points_occ:
@@ -218,7 +200,7 @@ def vote_labels(vox, labels, grid_size, fill=0, post_empty=None, out=None):
     count modulo 65 536, the lowest among equals.  ``post_empty`` (form C): a written 0 becomes 255, then ``post_empty`` becomes 0 --
     ``fill`` is written as given.  One radix sort and one run-length pass; the same bytes for every order of the rows."""
     g = _grid(grid_size)
-    vox, labels = _dev("vox", vox, torch.int32, dim=1), _dev("labels", labels, torch.uint8, dim=1)
+    vox, labels = device_tensor("vox", vox, torch.int32, dim=1), device_tensor("labels", labels, torch.uint8, dim=1)
     N = vox.shape[0]
     if labels.shape[0] != N or labels.device != vox.device:
         raise ValueError("vox [%d] on %s, labels [%d] on %s" % (N, vox.device, labels.shape[0], labels.device))
@@ -238,8 +220,8 @@ def vote_labels(vox, labels, grid_size, fill=0, post_empty=None, out=None):
 def visible_rows(centres, table, size):
     """uint8 ``[N]``: 1 where the centre (device fp32 ``[N,3]``) wins a pixel of any camera of ``table`` (device fp32 ``[n,28]``,
     ``depth_maps.camera_table``) at ``size = (H, W)`` -- the reference's per-camera z-buffer ``nb_process_img_points``."""
-    centres = _dev("centres", centres, torch.float32, 3)
-    table = _dev("table", table, torch.float32, depth_maps.CAM_FLOATS)
+    centres = device_tensor("centres", centres, torch.float32, 3)
+    table = device_tensor("table", table, torch.float32, depth_maps.CAM_FLOATS)
     H, W = int(size[0]), int(size[1])
     if not (1 <= H <= 32767 and 1 <= W <= 32767) or table.shape[0] < 1:
         raise ValueError("size (H, W) within 1 .. 32767 and one camera at least; got %s, %d cameras" % ((H, W), table.shape[0]))
@@ -280,11 +262,7 @@ def pose_doubles(results):
 def cloud_aabb(points, results):
     """fp32 ``[2,3]``: the min / max of the cloud (device fp32 ``[P >= 1, C >= 3]``) in the global frame -- lidar to ego, ego to global,
     in float64 on the device, rounded once.  A NaN coordinate makes the axes it reaches NaN, as numpy's min / max do."""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        _dev("points", points, torch.float32)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3 or points.shape[0] < 1:
-        raise ValueError("points must be float32 [P >= 1, C >= 3], got %s %s" % (points.dtype, tuple(points.shape)))
-    points = points.contiguous()
+    points = device_points(points, min_rows=1)
     aabb = torch.empty((2, 3), dtype=torch.float32, device=points.device)
     slots = core.stream_buffer(points.device, "occ_gt_aabb", 6, torch.int64)
     _lib.call("coocc_occ_cloud_aabb", ptr(points, torch.float32), points.shape[0], points.shape[1], _doubles(pose_doubles(results)), ptr(slots),
@@ -334,12 +312,7 @@ class _Loader:
         return bda_matrix(rotate_bda, scale_bda, fx, fy, fz)
 
     def _cloud(self, points):
-        if isinstance(points, torch.Tensor) and points.is_cuda:
-            return points
-        pts = points.numpy() if isinstance(points, torch.Tensor) else np.asarray(points)
-        if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] < 3:
-            raise ValueError("points must be float32 [P, C >= 3], got %s %s" % (pts.dtype, pts.shape))
-        return pts
+        return check_points(points if isinstance(points, torch.Tensor) else np.asarray(points))
 
     def _seg_bytes(self, lidarseg, P):
         seg = lidarseg.numpy() if isinstance(lidarseg, torch.Tensor) else np.asarray(lidarseg)
@@ -350,14 +323,6 @@ class _Loader:
         if missing.size:
             raise ValueError("lidarseg bytes %s are not in learning_map" % missing.tolist())
         return seg
-
-    def _upload(self, host):
-        """dict of host arrays (device tensors pass through) -> dict of device tensors, one staged copy"""
-        names = [k for k, v in host.items() if isinstance(v, np.ndarray)]
-        out = dict(host)
-        if names:
-            out.update(zip(names, self._stage([host[k] for k in names])))
-        return out
 
     def _table(self):
         if self._table_dev is None:
@@ -380,7 +345,7 @@ class _Loader:
     def _test_submit(self, points, img_inputs):
         """the is_test_submit form: the 9-tuple with the identity at index 6, points_occ with label 0"""
         out = {}
-        d = self._upload(dict(points=self._cloud(points), bda=np.eye(3, dtype=np.float32)))
+        d = self._stage.named(dict(points=self._cloud(points), bda=np.eye(3, dtype=np.float32)))
         if img_inputs is not None:
             if len(img_inputs) != 8:
                 raise ValueError("is_test_submit reads the 8-tuple (imgs, rots, trans, intrins, post_rots, post_trans, gt_depths, "
@@ -415,7 +380,7 @@ class LoadOccupancy(_Loader):
         if self.is_test_submit:
             return self._test_submit(points, img_inputs)
         bda = self._bda()
-        d = self._upload(dict(rows=pack_rows(occ, 3, self.grid, to_float32=True), points=self._cloud(points), bda=bda.numpy()))
+        d = self._stage.named(dict(rows=pack_rows(occ, 3, self.grid, to_float32=True), points=self._cloud(points), bda=bda.numpy()))
         out = dict(bda_rot=d["bda"], aabb=cloud_aabb(d["points"], results))
         out["gt_occ"] = self._cast(scatter_labels(d["rows"], self.grid, self.use_semantic), dtype)
         self._tuples(out, img_inputs, gt_depths, d["bda"], out["aabb"], True)
@@ -457,7 +422,7 @@ class LoadOccupancy2(_Loader):
         if self.cal_visible and img_inputs is not None and table is None:
             small = [t.cpu() for t in img_inputs[1:6]]
             host["cams"] = depth_maps.camera_table(*small).numpy()
-        d = self._upload(host)
+        d = self._stage.named(host)
         out = dict(bda_rot=d["bda"], aabb=cloud_aabb(d["points"], results))
         out["points_occ"] = points_to_voxels(d["points"], "none", bda_rot=bda, lidarseg=d["seg"], table=self._table(), points_occ=True)[2]
         vox, labels, centres = rows_to_voxels(d["rows"], self.grid, self.pc_range, bda, centres=self.cal_visible)
@@ -490,7 +455,7 @@ class LoadNuscOccupancyAnnotations(_Loader):
             return self._test_submit(points, img_inputs)
         bda = self._bda()
         pts = self._cloud(points)
-        d = self._upload(dict(points=pts, bda=bda.numpy(), seg=self._seg_bytes(lidarseg, pts.shape[0])))
+        d = self._stage.named(dict(points=pts, bda=bda.numpy(), seg=self._seg_bytes(lidarseg, pts.shape[0])))
         out = dict(bda_rot=d["bda"], aabb=cloud_aabb(d["points"], results))
         vox, labels, out["points_occ"] = points_to_voxels(d["points"], "annotation", self.grid, self.pc_range, bda, d["seg"], self._table(),
                                                           points_occ=True)

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib, core
-from ._lib import CooccError, ptr
-from .depth_maps import HostStage
+from ._lib import ptr, require_gpu
+from .staging import HostStage, device_tensor, pinned_upload
 
 # struct coocc_sweep_seg (include/coocc_hip.h), 128 bytes
 SEG_DTYPE = np.dtype([("in_row0", "<i8"), ("n_rows", "<i8"), ("out_row0", "<i8"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("dt", "<f4"),
@@ -78,10 +78,9 @@ class SweepTable:
     def to(self, device):
         """Upload the records (pinned, asynchronous) unless they are there already."""
         device = torch.device(device)
-        if device.type != "cuda":
-            raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % device)
+        require_gpu(device)
         if self.dev is None or self.dev.device != device:
-            self.dev = torch.from_numpy(self.segs.view(np.uint8).copy()).pin_memory().to(device, non_blocking=True)
+            self.dev = pinned_upload(torch.from_numpy(self.segs.view(np.uint8)), device)[0]
         return self
 
 
@@ -135,13 +134,8 @@ def merge_sweeps(raw, table, use_dim=(0, 1, 2, 4), radius=1.0, out=None, count=N
     ``[1]`` on the device, optional) = ``table.total``; capturable into a graph with no parallel branches.  With filtering: three
     launches, ``out`` is the padded buffer of which rows ``[0, count)`` are written, ``count`` is made when not given.  Never reads the
     host.  ``out`` and ``count`` are written in place when given.  ``radius``: compared as ``float32(radius)``."""
-    if not isinstance(raw, torch.Tensor):
-        raise ValueError("raw must be a tensor, got %s" % type(raw).__name__)
-    if not raw.is_cuda:
-        raise CooccError("co_occ_amd ops run on the GPU only; got a %s tensor (no CPU fallback)" % raw.device)
-    if raw.dtype != torch.float32:
-        raise ValueError("raw must be float32, got %s" % raw.dtype)
-    if raw.dim() != 2 or raw.shape[0] != table.in_rows:
+    raw = device_tensor("raw", raw, torch.float32)
+    if raw.shape[0] != table.in_rows:
         raise ValueError("raw must be [%d, load_dim], got %s" % (table.in_rows, tuple(raw.shape)))
     cols = use_columns(use_dim, raw.shape[1])
     dev = raw.device
@@ -161,7 +155,7 @@ def merge_sweeps(raw, table, use_dim=(0, 1, 2, 4), radius=1.0, out=None, count=N
     ws = None
     if table.filtering:
         ws = core.stream_buffer(dev, "sweeps", int(_lib.load().coocc_sweeps_merge_ws(table.total)), torch.uint8)
-    _lib.call("coocc_sweeps_merge", ptr(raw.contiguous(), torch.float32), table.in_rows, raw.shape[1], ptr(table.dev),
+    _lib.call("coocc_sweeps_merge", ptr(raw, torch.float32), table.in_rows, raw.shape[1], ptr(table.dev),
               ctypes.c_void_p(table.segs.ctypes.data), len(table.segs), _lib.host_i32(cols), len(cols), float(np.float32(radius)),
               ptr(out, torch.float32), table.total, ptr(count), ptr(ws), 0 if ws is None else ws.numel())
     return out, count
@@ -204,15 +198,14 @@ class LoadPointsFromMultiSweeps:
             raise ValueError("sweeps_num must be 0 .. %d, got %d" % (MAX_SWEEPS, sweeps_num))
         self.sweeps_num, self.pad_empty_sweeps, self.remove_close, self.test_mode = int(sweeps_num), pad_empty_sweeps, remove_close, test_mode
         self.device, self.rng, self.radius = torch.device(device), rng, 1.0
-        self._stage = None
+        self._stage = HostStage(self.device)
 
     def __call__(self, points, sweeps, timestamp):
         """``points``: the key-frame cloud (a numpy array, a CPU tensor, a path, or bytes); ``sweeps``: the info dict's list, each entry
         ``'data_path'`` or an in-memory ``'points'`` array, ``'sensor2lidar_rotation'``, ``'sensor2lidar_translation'``, ``'timestamp'``;
         ``timestamp``: the sample's, in seconds.  Returns ``(cloud, extras)``: ``cloud`` device fp32 ``[P, len(use_dim)]``; ``extras``
         holds ``choices``, ``rows`` (per segment, before filtering), ``upload_bytes`` and ``count`` (int32 ``[1]`` on the device)."""
-        if self.device.type != "cuda":
-            raise CooccError("co_occ_amd ops run on the GPU only; got device %s (no CPU fallback)" % self.device)
+        require_gpu(self.device)
         key = read_points(points, self.load_dim)
         padded = self.pad_empty_sweeps and len(sweeps) == 0
         choices = np.arange(0) if padded else choose_sweeps(len(sweeps), self.sweeps_num, self.test_mode, self.rng)
@@ -220,8 +213,6 @@ class LoadPointsFromMultiSweeps:
                           for i in choices]
         table = sweep_table(len(key), sweeps, timestamp, choices, [len(c) for c in clouds[1:]], self.sweeps_num, self.pad_empty_sweeps,
                             self.remove_close)
-        if self._stage is None:
-            self._stage = HostStage(self.device)
         raw, table.dev = self._stage([tuple(clouds), table.segs.view(np.uint8)])          # one pinned buffer, one copy
         count = torch.empty(1, dtype=torch.int32, device=self.device)
         out, count = merge_sweeps(raw.view(table.in_rows, self.load_dim), table, self.use_dim, self.radius, count=count)

@@ -12,7 +12,7 @@ import torch
 import depth_map_refs as D
 import image_input_refs as R
 from conftest import GOLDEN
-from co_occ_amd import _lib, depth_maps as DM, image_inputs as II
+from co_occ_amd import _lib, depth_maps as DM, image_inputs as II, staging
 from co_occ_amd._lib import CooccError
 
 SIZES = {"R50": R.R50, "R101": R.R101}
@@ -203,7 +203,7 @@ def test_python_refusals_without_a_gpu():
         DM.points_to_depth_maps(pts, table, (4, 4))
     with pytest.raises(ValueError, match="tensor"):
         DM.points_to_depth_maps(pts.numpy(), table, (4, 4))
-    stage = DM.PointStage("cuda")
+    stage = staging.PointStage("cuda")
     with pytest.raises(ValueError, match="float32"):
         stage(np.zeros((4, 3), np.float64))
     with pytest.raises(ValueError, match="C >= 3"):
