@@ -93,6 +93,14 @@ SIGNATURES = {
     "coocc_conv_fwd": (I, [ctypes.POINTER(ConvDesc), P]),
     "coocc_fuser_search_ws": (Z, [ctypes.POINTER(SearchDesc)]),
     "coocc_fuser_search": (I, [ctypes.POINTER(SearchDesc), P, P]),
+    "coocc_fuser_search_oneshot": (I, [I]),
+    "coocc_lin_to_coords_dev": (I, [P, I, P, I, I, I, I, I, P, P]),
+    "coocc_fps_voxels_pair_ok": (I, [I, I, I, I]),
+    "coocc_fps_voxels_pair_dev": (I, [P, I, P, P, P, I, P, P, Z, I, P, I, I, I, I, I, P]),
+    "coocc_knn_topk_voxels_dev": (I, [I, I, I, I, I, P, P, P, P, I, P, P, P, P, P, I, I, P]),
+    "coocc_ball_query_voxels_dev": (I, [I, F, F, I, I, I, I, P, P, P, P, P, I, P]),
+    "coocc_knn_assign_dev": (I, [I, I, I, I, F, P, P, P, P, P, P, I, I, P]),
+    "coocc_index_rows_i32_dev": (I, [P, I, P, I, I, I, P, P, I, P]),
     "coocc_upsample_add_trilinear": (I, [P, P, I, I, I, I, I, I, I, I, P]),
     "coocc_upsample_add_trilinear_ex": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
     "coocc_occhead_mix": (I, [P, P, I, P, P, I, I, P]),

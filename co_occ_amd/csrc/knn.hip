@@ -169,8 +169,44 @@ extern "C" int coocc_furthest_point_sampling(int b, int n, int m, const float* p
 // every reduction on the per-sample critical path.
 struct FpsCell { int temp; int r; };
 
+// The tie-rank layout of a list of n voxels on a grid whose largest squared distance is d2max: block = 1 << L, q blocks, ranks in
+// RB bits; key32: temp and rank share one 32-bit key.  ONE formula for the host (fps_prepare, the eligibility of the paired
+// launch) and for the kernels that read n on the device (the one-shot search, csrc/search.hip).  RB never decreases with n, so a
+// grid that is key32 at n = X*Y*Z is key32 for every list on it.
+struct FpsRank { int L, q, RB, tinit; bool key32; };
+__host__ __device__ inline FpsRank fps_rank_layout(int n, long long d2max) {
+  FpsRank r;
+  int L = 0;
+  while ((2 << L) <= n && L < 10) ++L;            // block = min(2^floor(log2 n), 1024) = 1 << L
+  const int q = (n + (1 << L) - 1) >> L;          // tie ranks live in [0, q << L)
+  int RB = L;
+  while ((1ll << RB) <= ((long long)q << L)) ++RB;   // strict: rank rmask is never used, key 0 stays "empty"
+  r.key32 = RB < 31 && d2max + 1 < (1ll << (32 - RB)) - 1;
+  r.tinit = r.key32 ? (int)((1u << (32 - RB)) - 1u) : 0x7FFFFFFF;
+  r.L = L; r.q = q; r.RB = RB;
+  return r;
+}
+static inline long long fps_d2max(int X, int Y, int Z) {
+  return (long long)(X - 1) * (X - 1) + (long long)(Y - 1) * (Y - 1) + (long long)(Z - 1) * (Z - 1);
+}
+
+// Device-count forms (one-shot search): `cnt` = the two list lengths of the stage on the device (img, pts), cnt[which] the length
+// this launch works on; the grid is sized for the capacity and surplus threads leave at once.  When either list is not longer
+// than small_m the stage takes the reference's other branch on the host, and every kernel leaves before it writes anything.
+// cnt == nullptr: the lengths are the host's arguments.
+__device__ __forceinline__ bool dev_counts_small(const int32_t* __restrict__ cnt, int small_m) {
+  return cnt[0] <= small_m || cnt[1] <= small_m;
+}
+
 __global__ __launch_bounds__(256) void k_fpsv_scatter(const int32_t* __restrict__ lin, int n, int Y, int Z, int NBY,
-                                                       int NBZ, int L, int q, int tinit, FpsCell* __restrict__ cell) {
+                                                       int NBZ, int L, int q, int tinit, FpsCell* __restrict__ cell,
+                                                       const int32_t* __restrict__ cnt, int which, int small_m, long long d2max) {
+  if (cnt) {
+    if (dev_counts_small(cnt, small_m)) return;
+    n = min(n, cnt[which]);
+    const FpsRank r = fps_rank_layout(n, d2max);
+    L = r.L; q = r.q; tinit = r.tinit;
+  }
   int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   int l = lin[k];
@@ -405,17 +441,25 @@ __global__ __launch_bounds__(THREADS) void k_fps_voxels(int n, int m, int Y, int
 // 127 of them).  Same arithmetic, same selections as k_fps_voxels (and so as the reference kernel).  gridDim.x = number of
 // independent problems: the two search directions of BiFuser_N run as ONE launch, one workgroup (= one CU) each.
 #define FPSR_SLOTS 40
-struct FpsRegProblem { const int32_t* lin; const FpsCell* cell; int32_t* idx; int n, L, q, RB; };
-struct FpsRegArgs { FpsRegProblem p[2]; int m, Y, Z, NBY, NBZ, NB; long long* dbg; };
+struct FpsRegProblem { const int32_t* lin; const FpsCell* cell; int32_t* idx; int n, L, q, RB, which; };
+// cnt != nullptr (device-count form): problem p works on a list of cnt[p.which] voxels and derives its tie-rank layout from that
+// length itself (p.n / L / q / RB unused); the whole launch leaves before its first write when a list is not longer than small_m
+struct FpsRegArgs { FpsRegProblem p[2]; int m, Y, Z, NBY, NBZ, NB; long long* dbg; const int32_t* cnt; int small_m; long long d2max; };
 
 __global__ __launch_bounds__(1024) void k_fps_voxels_reg(FpsRegArgs a) {
   constexpr int NW = 16;
+  if (a.cnt && dev_counts_small(a.cnt, a.small_m)) return;     // uniform over the launch, ahead of every barrier and store
   __builtin_amdgcn_s_setprio(3);
   __shared__ unsigned wbest[2][NW];
   __shared__ int wloc[2][NW];
   const FpsRegProblem pr = a.p[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int RB = pr.RB, Y = a.Y, Z = a.Z, NB = a.NB, m = a.m;
+  int pL = pr.L, pq = pr.q, pRB = pr.RB;
+  if (a.cnt) {
+    const FpsRank rk = fps_rank_layout(a.cnt[pr.which], a.d2max);
+    pL = rk.L; pq = rk.q; pRB = rk.RB;
+  }
+  const int RB = pRB, Y = a.Y, Z = a.Z, NB = a.NB, m = a.m;
   const unsigned rmask = (1u << RB) - 1u;
   const unsigned tmax = (1u << (32 - RB)) - 1u;
   long long* dbg = a.dbg;
@@ -525,9 +569,9 @@ __global__ __launch_bounds__(1024) void k_fps_voxels_reg(FpsRegArgs a) {
   __syncthreads();
   for (int j = 1 + tid; j < m; j += 1024) {
     const unsigned rr = rmask - (unsigned)pr.idx[j];
-    const unsigned hi = rr / (unsigned)pr.q, lo = rr - hi * (unsigned)pr.q;
-    const unsigned rev = pr.L ? (__brev(hi) >> (32 - pr.L)) : 0u;
-    pr.idx[j] = (int)((lo << pr.L) | rev);
+    const unsigned hi = rr / (unsigned)pq, lo = rr - hi * (unsigned)pq;
+    const unsigned rev = pL ? (__brev(hi) >> (32 - pL)) : 0u;
+    pr.idx[j] = (int)((lo << pL) | rev);
   }
   if (dbg && lane == 0 && blockIdx.x == 0) {
     long long* o = dbg + wave * 8;
@@ -548,8 +592,10 @@ extern "C" void coocc_fps_voxels_set_threads(int t) { g_fps_threads = t; }
 struct FpsPrep { int NBX, NBY, NBZ, L, q, RB, tinit, threads, R; long long NB; bool key32; };
 
 // argument checks + tie-rank layout + the initial cell table ({tinit, rank} per position, -1 = empty): memset + scatter
+// cnt != nullptr: n is the capacity of the list, its length is cnt[which] on the device (the scatter derives the layout there; the
+// FpsPrep fields L, q, RB, tinit are then those of a list of n voxels, the hardest case)
 static int fps_prepare(const int32_t* lin, int n, int X, int Y, int Z, int m, const int32_t* idx, void* ws, size_t ws_bytes,
-                       hipStream_t s, FpsPrep* o) {
+                       hipStream_t s, FpsPrep* o, const int32_t* cnt = nullptr, int which = 0, int small_m = 0) {
   COOCC_CHECK_ARG(lin && idx && ws && n > 0 && m >= 0 && X > 0 && Y > 0 && Z > 0, "fps_voxels: bad args");
   COOCC_CHECK_ARG(n < (1 << FPS_KBITS), "fps_voxels: n must be < 2^22");
   COOCC_CHECK_ARG(X <= 1020 && Y <= 1020 && Z <= 1016, "fps_voxels: grid dims must fit 10-bit packed coordinates");
@@ -563,19 +609,17 @@ static int fps_prepare(const int32_t* lin, int n, int X, int Y, int Z, int m, co
   if (ws_bytes < coocc_fps_voxels_ws(X, Y, Z)) return coocc_set_error(COOCC_ENOMEM, "fps_voxels: workspace too small");
   o->threads = threads;
   o->R = (int)((o->NB + threads - 1) / threads);
-  int L = 0;
-  while ((2 << L) <= n && L < 10) ++L;            // block = min(2^floor(log2 n), 1024) = 1 << L
-  const int q = (n + (1 << L) - 1) >> L;          // tie ranks live in [0, q << L)
-  int RB = L;
-  while ((1ll << RB) <= ((long long)q << L)) ++RB;   // strict: rank rmask is never used, key 0 stays "empty"
-  const long long d2max = (long long)(X - 1) * (X - 1) + (long long)(Y - 1) * (Y - 1) + (long long)(Z - 1) * (Z - 1);
-  o->key32 = RB < 31 && d2max + 1 < (1ll << (32 - RB)) - 1;
-  o->tinit = o->key32 ? (int)((1u << (32 - RB)) - 1u) : 0x7FFFFFFF;
-  o->L = L; o->q = q; o->RB = RB;
+  const long long d2max = fps_d2max(X, Y, Z);
+  const FpsRank rk = fps_rank_layout(n, d2max);
+  const int L = rk.L, q = rk.q;
+  o->key32 = rk.key32;
+  o->tinit = rk.tinit;
+  o->L = L; o->q = q; o->RB = rk.RB;
   if (m == 0) return COOCC_OK;
   FpsCell* cell = (FpsCell*)ws;
   COOCC_HIP(hipMemsetAsync(cell, 0xFF, sizeof(FpsCell) * (size_t)o->NB * FT_P, s));
-  hipLaunchKernelGGL(k_fpsv_scatter, dim3(cdiv(n, 256)), dim3(256), 0, s, lin, n, Y, Z, o->NBY, o->NBZ, L, q, o->tinit, cell);
+  hipLaunchKernelGGL(k_fpsv_scatter, dim3(cdiv(n, 256)), dim3(256), 0, s, lin, n, Y, Z, o->NBY, o->NBZ, L, q, o->tinit, cell, cnt, which,
+                     small_m, d2max);
   COOCC_LAUNCH_CHECK("k_fpsv_scatter");
   return COOCC_OK;
 }
@@ -584,6 +628,17 @@ static int g_fps_reg = -1;      // COOCC_FPS_REG=0: always the L2-resident kerne
 static bool fps_reg_ok(const FpsPrep& o) {
   if (g_fps_reg < 0) g_fps_reg = getenv("COOCC_FPS_REG") ? atoi(getenv("COOCC_FPS_REG")) : 1;
   return g_fps_reg && o.key32 && o.NB <= (long long)FPSR_SLOTS * 16;
+}
+
+// 1 when the paired register-resident launch takes lists of up to n voxels on this grid (same rules as fps_prepare / fps_reg_ok;
+// RB does not decrease with n, so n is the hardest length), else 0.  Host arithmetic only.
+extern "C" int coocc_fps_voxels_pair_ok(int n, int X, int Y, int Z) {
+  if (n <= 0 || X <= 0 || Y <= 0 || Z <= 0 || n >= (1 << FPS_KBITS)) return 0;
+  const long long NB = (long long)((X + FT_X - 1) / FT_X) * ((Y + FT_Y - 1) / FT_Y) * ((Z + FT_Z - 1) / FT_Z);
+  if (NB > (long long)FPSR_SLOTS * 16) return 0;
+  if (!fps_rank_layout(n, fps_d2max(X, Y, Z)).key32) return 0;
+  if (g_fps_reg < 0) g_fps_reg = getenv("COOCC_FPS_REG") ? atoi(getenv("COOCC_FPS_REG")) : 1;
+  return g_fps_reg ? 1 : 0;
 }
 
 extern "C" int coocc_fps_voxels(const int32_t* lin, int n, int X, int Y, int Z, int m, int32_t* idx, void* ws,
@@ -634,22 +689,8 @@ extern "C" int coocc_fps_voxels(const int32_t* lin, int n, int X, int Y, int Z, 
 extern "C" int coocc_fps_voxels_pair(const int32_t* lin0, int n0, int32_t* idx0, void* ws0, const int32_t* lin1, int n1, int32_t* idx1,
                                      void* ws1, size_t ws_bytes_each, int X, int Y, int Z, int m, void* stream) {
   COOCC_CHECK_ARG(X > 0 && Y > 0 && Z > 0 && n0 > 0 && n1 > 0, "fps_voxels_pair: bad args");
-  {
-    // eligibility before anything is enqueued (same rules as fps_prepare / fps_reg_ok)
-    const long long NB = (long long)((X + FT_X - 1) / FT_X) * ((Y + FT_Y - 1) / FT_Y) * ((Z + FT_Z - 1) / FT_Z);
-    if (NB > (long long)FPSR_SLOTS * 16) return 2;
-    const long long d2max = (long long)(X - 1) * (X - 1) + (long long)(Y - 1) * (Y - 1) + (long long)(Z - 1) * (Z - 1);
-    for (int n : {n0, n1}) {
-      int L = 0;
-      while ((2 << L) <= n && L < 10) ++L;
-      const int q = (n + (1 << L) - 1) >> L;
-      int RB = L;
-      while ((1ll << RB) <= ((long long)q << L)) ++RB;
-      if (!(RB < 31 && d2max + 1 < (1ll << (32 - RB)) - 1)) return 2;
-    }
-    if (g_fps_reg < 0) g_fps_reg = getenv("COOCC_FPS_REG") ? atoi(getenv("COOCC_FPS_REG")) : 1;
-    if (!g_fps_reg) return 2;
-  }
+  // eligibility before anything is enqueued (same rules as fps_prepare / fps_reg_ok)
+  if (!coocc_fps_voxels_pair_ok(n0, X, Y, Z) || !coocc_fps_voxels_pair_ok(n1, X, Y, Z)) return 2;
   hipStream_t s = as_stream(stream);
   FpsPrep o0, o1;
   int rc = fps_prepare(lin0, n0, X, Y, Z, m, idx0, ws0, ws_bytes_each, s, &o0);
@@ -660,6 +701,31 @@ extern "C" int coocc_fps_voxels_pair(const int32_t* lin0, int n0, int32_t* idx0,
   a.p[0] = FpsRegProblem{lin0, (const FpsCell*)ws0, idx0, n0, o0.L, o0.q, o0.RB};
   a.p[1] = FpsRegProblem{lin1, (const FpsCell*)ws1, idx1, n1, o1.L, o1.q, o1.RB};
   a.m = m; a.Y = Y; a.Z = Z; a.NBY = o0.NBY; a.NBZ = o0.NBZ; a.NB = (int)o0.NB; a.dbg = g_fps_dbg;
+  hipLaunchKernelGGL(k_fps_voxels_reg, dim3(2), dim3(1024), 0, s, a);
+  COOCC_LAUNCH_CHECK("k_fps_voxels_reg");
+  return COOCC_OK;
+}
+
+// The paired launch with the list lengths read on the device: problem i works on lin_i[0 .. cnt[which_i]), at most n_cap entries
+// each.  Eligibility is decided for lists of n_cap voxels (coocc_fps_voxels_pair_ok; 2 = not taken, nothing enqueued).  Nothing
+// is written when cnt[0] <= small_m or cnt[1] <= small_m.
+extern "C" int coocc_fps_voxels_pair_dev(const int32_t* lin0, int which0, int32_t* idx0, void* ws0, const int32_t* lin1, int which1,
+                                         int32_t* idx1, void* ws1, size_t ws_bytes_each, int n_cap, const int32_t* cnt, int small_m,
+                                         int X, int Y, int Z, int m, void* stream) {
+  COOCC_CHECK_ARG(X > 0 && Y > 0 && Z > 0 && n_cap > 0 && cnt && (unsigned)which0 < 2u && (unsigned)which1 < 2u && small_m >= m,
+                  "fps_voxels_pair_dev: bad args");
+  if (!coocc_fps_voxels_pair_ok(n_cap, X, Y, Z)) return 2;
+  hipStream_t s = as_stream(stream);
+  FpsPrep o0, o1;
+  int rc = fps_prepare(lin0, n_cap, X, Y, Z, m, idx0, ws0, ws_bytes_each, s, &o0, cnt, which0, small_m);
+  if (rc != COOCC_OK) return rc;
+  rc = fps_prepare(lin1, n_cap, X, Y, Z, m, idx1, ws1, ws_bytes_each, s, &o1, cnt, which1, small_m);
+  if (rc != COOCC_OK || m == 0) return rc;
+  FpsRegArgs a = {};
+  a.p[0] = FpsRegProblem{lin0, (const FpsCell*)ws0, idx0, 0, 0, 0, 0, which0};
+  a.p[1] = FpsRegProblem{lin1, (const FpsCell*)ws1, idx1, 0, 0, 0, 0, which1};
+  a.m = m; a.Y = Y; a.Z = Z; a.NBY = o0.NBY; a.NBZ = o0.NBZ; a.NB = (int)o0.NB; a.dbg = g_fps_dbg;
+  a.cnt = cnt; a.small_m = small_m; a.d2max = fps_d2max(X, Y, Z);
   hipLaunchKernelGGL(k_fps_voxels_reg, dim3(2), dim3(1024), 0, s, a);
   COOCC_LAUNCH_CHECK("k_fps_voxels_reg");
   return COOCC_OK;
@@ -822,7 +888,9 @@ extern "C" int coocc_voxel_index_map(const int32_t* lin, int n, int nvox, int32_
 // centres: list ordinals into the QUERY list (its voxels are lin_q[ord]); map_q: voxel -> query ordinal.
 __global__ __launch_bounds__(256) void k_ball_query_vox(int m, float min_r2, float max_r2, int R, int nsample, int X, int Y, int Z,
                                                          const int32_t* __restrict__ centre_ord, const int32_t* __restrict__ lin_q,
-                                                         const int32_t* __restrict__ map_q, int32_t* __restrict__ idx_all) {
+                                                         const int32_t* __restrict__ map_q, int32_t* __restrict__ idx_all,
+                                                         const int32_t* __restrict__ dcnt, int small_m) {
+  if (dcnt && dev_counts_small(dcnt, small_m)) return;
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= m) return;
@@ -858,18 +926,31 @@ __global__ __launch_bounds__(256) void k_ball_query_vox(int m, float min_r2, flo
   for (int l = cnt + lane; l < nsample; l += 64) idx[l] = first;  // first == 0 when no hit
 }
 
-extern "C" int coocc_ball_query_voxels(int m, float min_radius, float max_radius, int nsample, int X, int Y, int Z,
-                                       const int32_t* centre_ord, const int32_t* lin_q, const int32_t* map_q, int32_t* idx,
-                                       void* stream) {
+static int ball_query_voxels(int m, float min_radius, float max_radius, int nsample, int X, int Y, int Z, const int32_t* centre_ord,
+                             const int32_t* lin_q, const int32_t* map_q, int32_t* idx, const int32_t* cnt, int small_m, void* stream) {
   COOCC_CHECK_ARG(m > 0 && nsample > 0 && X > 0 && Y > 0 && Z > 0 && centre_ord && lin_q && map_q && idx, "ball_query_voxels: bad args");
   COOCC_CHECK_ARG(max_radius >= 0.f && max_radius < 4096.f, "ball_query_voxels: bad radius");
   const float max_r2 = max_radius * max_radius;
   int R = (int)ceilf(max_radius);
   while (R > 0 && (float)(R * R) >= max_r2) --R;          // largest R with R^2 < max_r2 (hits need d^2 < max_r2, or d^2 == 0)
   hipLaunchKernelGGL(k_ball_query_vox, dim3(cdiv(m, 4)), dim3(256), 0, as_stream(stream), m, min_radius * min_radius, max_r2, R,
-                     nsample, X, Y, Z, centre_ord, lin_q, map_q, idx);
+                     nsample, X, Y, Z, centre_ord, lin_q, map_q, idx, cnt, small_m);
   COOCC_LAUNCH_CHECK("k_ball_query_vox");
   return COOCC_OK;
+}
+
+extern "C" int coocc_ball_query_voxels(int m, float min_radius, float max_radius, int nsample, int X, int Y, int Z,
+                                       const int32_t* centre_ord, const int32_t* lin_q, const int32_t* map_q, int32_t* idx,
+                                       void* stream) {
+  return ball_query_voxels(m, min_radius, max_radius, nsample, X, Y, Z, centre_ord, lin_q, map_q, idx, nullptr, 0, stream);
+}
+
+// the same launch inside a one-shot search: nothing is written when cnt[0] <= small_m or cnt[1] <= small_m (device counts)
+extern "C" int coocc_ball_query_voxels_dev(int m, float min_radius, float max_radius, int nsample, int X, int Y, int Z,
+                                           const int32_t* centre_ord, const int32_t* lin_q, const int32_t* map_q, int32_t* idx,
+                                           const int32_t* cnt, int small_m, void* stream) {
+  COOCC_CHECK_ARG(cnt, "ball_query_voxels_dev: null counts");
+  return ball_query_voxels(m, min_radius, max_radius, nsample, X, Y, Z, centre_ord, lin_q, map_q, idx, cnt, small_m, stream);
 }
 
 // offsets: [noff] packed (dx + 128) | (dy + 128) << 8 | (dz + 128) << 16, sorted by (d^2, dx, dy, dz); every offset with
@@ -878,7 +959,8 @@ template <int K>
 __global__ __launch_bounds__(256) void k_knn_topk_vox(int nq, int X, int Y, int Z, const int32_t* __restrict__ rep_ord,
                                                        const int32_t* __restrict__ lin_q, const int32_t* __restrict__ map_k,
                                                        const uint32_t* __restrict__ offsets, int noff, float* __restrict__ val,
-                                                       int32_t* __restrict__ idx) {
+                                                       int32_t* __restrict__ idx, const int32_t* __restrict__ cnt, int small_m) {
+  if (cnt && dev_counts_small(cnt, small_m)) return;
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= nq) return;
@@ -913,7 +995,12 @@ __global__ __launch_bounds__(256) void k_knn_topk_vox(int nq, int X, int Y, int 
 template <int K>
 __global__ __launch_bounds__(256) void k_knn_topk_unresolved(int nq, int nk, const float* __restrict__ q,
                                                               const float* __restrict__ key, float* __restrict__ val,
-                                                              int32_t* __restrict__ idx) {
+                                                              int32_t* __restrict__ idx, const int32_t* __restrict__ cnt, int which,
+                                                              int small_m) {
+  if (cnt) {                                   // nk: the key list's length on the device
+    if (dev_counts_small(cnt, small_m)) return;
+    nk = cnt[which];
+  }
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= nq || idx[(size_t)r * K] != -2) return;
@@ -950,30 +1037,45 @@ __global__ __launch_bounds__(256) void k_knn_topk_unresolved(int nq, int nk, con
 template <int K>
 static void launch_topk_vox(int nq, int nk, int X, int Y, int Z, const int32_t* rep_ord, const int32_t* lin_q, const int32_t* map_k,
                             const uint32_t* offsets, int noff, const float* q, const float* key, float* val, int32_t* idx,
-                            hipStream_t s) {
-  hipLaunchKernelGGL(k_knn_topk_vox<K>, dim3(cdiv(nq, 4)), dim3(256), 0, s, nq, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, val, idx);
-  hipLaunchKernelGGL(k_knn_topk_unresolved<K>, dim3(cdiv(nq, 4)), dim3(256), 0, s, nq, nk, q, key, val, idx);
+                            const int32_t* cnt, int which, int small_m, hipStream_t s) {
+  hipLaunchKernelGGL(k_knn_topk_vox<K>, dim3(cdiv(nq, 4)), dim3(256), 0, s, nq, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, val, idx,
+                     cnt, small_m);
+  hipLaunchKernelGGL(k_knn_topk_unresolved<K>, dim3(cdiv(nq, 4)), dim3(256), 0, s, nq, nk, q, key, val, idx, cnt, which, small_m);
 }
 
-extern "C" int coocc_knn_topk_voxels(int nq, int nk, int K, int X, int Y, int Z, const int32_t* rep_ord, const int32_t* lin_q,
-                                     const int32_t* map_k, const uint32_t* offsets, int noff, const float* q, const float* key,
-                                     float* val, int32_t* idx, void* stream) {
+static int knn_topk_voxels(int nq, int nk, int K, int X, int Y, int Z, const int32_t* rep_ord, const int32_t* lin_q,
+                           const int32_t* map_k, const uint32_t* offsets, int noff, const float* q, const float* key, float* val,
+                           int32_t* idx, const int32_t* cnt, int which, int small_m, void* stream) {
   COOCC_CHECK_ARG(nq > 0 && nk > 0 && X > 0 && Y > 0 && Z > 0 && rep_ord && lin_q && map_k && offsets && noff > 0 && q && key &&
                       val && idx, "knn_topk_voxels: bad args");
   COOCC_CHECK_ARG(K >= 1 && K <= 8 && K <= nk, "knn_topk_voxels: need 1 <= K <= min(8, nk)");
   hipStream_t s = as_stream(stream);
   switch (K) {
-    case 1: launch_topk_vox<1>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    case 2: launch_topk_vox<2>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    case 3: launch_topk_vox<3>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    case 4: launch_topk_vox<4>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    case 5: launch_topk_vox<5>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    case 6: launch_topk_vox<6>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    case 7: launch_topk_vox<7>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
-    default: launch_topk_vox<8>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, s); break;
+    case 1: launch_topk_vox<1>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    case 2: launch_topk_vox<2>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    case 3: launch_topk_vox<3>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    case 4: launch_topk_vox<4>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    case 5: launch_topk_vox<5>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    case 6: launch_topk_vox<6>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    case 7: launch_topk_vox<7>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
+    default: launch_topk_vox<8>(nq, nk, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, s); break;
   }
   COOCC_LAUNCH_CHECK("k_knn_topk_vox");
   return COOCC_OK;
+}
+
+extern "C" int coocc_knn_topk_voxels(int nq, int nk, int K, int X, int Y, int Z, const int32_t* rep_ord, const int32_t* lin_q,
+                                     const int32_t* map_k, const uint32_t* offsets, int noff, const float* q, const float* key,
+                                     float* val, int32_t* idx, void* stream) {
+  return knn_topk_voxels(nq, nk, K, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, nullptr, 0, 0, stream);
+}
+
+// the key list's length read on the device (cnt[which], more than small_m >= K entries or nothing is written; device counts above)
+extern "C" int coocc_knn_topk_voxels_dev(int nq, int K, int X, int Y, int Z, const int32_t* rep_ord, const int32_t* lin_q,
+                                         const int32_t* map_k, const uint32_t* offsets, int noff, const float* q, const float* key,
+                                         float* val, int32_t* idx, const int32_t* cnt, int which, int small_m, void* stream) {
+  COOCC_CHECK_ARG(cnt && (unsigned)which < 2u && small_m >= K, "knn_topk_voxels_dev: bad counts");
+  return knn_topk_voxels(nq, small_m + 1, K, X, Y, Z, rep_ord, lin_q, map_k, offsets, noff, q, key, val, idx, cnt, which, small_m, stream);
 }
 
 // ------------------------------------------------------------------ K5: assignment
@@ -981,7 +1083,12 @@ extern "C" int coocc_knn_topk_voxels(int nq, int nk, int K, int X, int Y, int Z,
 // centres overriding earlier ones.  atomicMax on the centre ordinal makes "last writer wins"
 // deterministic; a second pass translates the winning centre into its k-th key.
 __global__ void k_assign_winner(int nc, int K, int ns, int nq, float thresh, const float* __restrict__ val,
-                                const int32_t* __restrict__ group, int32_t* __restrict__ winner) {
+                                const int32_t* __restrict__ group, int32_t* __restrict__ winner, const int32_t* __restrict__ cnt,
+                                int which, int small_m) {
+  if (cnt) {                                   // nq (the stride of `winner`): the query list's length on the device
+    if (dev_counts_small(cnt, small_m)) return;
+    nq = cnt[which];
+  }
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nc * ns) return;
   int c = i / ns;
@@ -995,7 +1102,12 @@ __global__ void k_assign_winner(int nc, int K, int ns, int nq, float thresh, con
 }
 
 __global__ void k_assign_lookup(int K, int nq, const int32_t* __restrict__ nn,
-                                const int32_t* __restrict__ winner, int32_t* __restrict__ out) {
+                                const int32_t* __restrict__ winner, int32_t* __restrict__ out, const int32_t* __restrict__ cnt,
+                                int which, int small_m) {
+  if (cnt) {
+    if (dev_counts_small(cnt, small_m)) return;
+    nq = cnt[which];
+  }
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= K * nq) return;
   int k = i / nq;
@@ -1003,17 +1115,31 @@ __global__ void k_assign_lookup(int K, int nq, const int32_t* __restrict__ nn,
   out[i] = w >= 0 ? nn[w * K + k] : -1;
 }
 
-extern "C" int coocc_knn_assign(int nc, int K, int ns, int nq, float dist_thresh, const float* val,
-                                const int32_t* nn, const int32_t* group, int32_t* winner, int32_t* out,
-                                void* stream) {
+// cnt != nullptr: nq is the capacity of the query list (fill and grids sized by it), its length is cnt[which] on the device
+static int knn_assign(int nc, int K, int ns, int nq, float dist_thresh, const float* val, const int32_t* nn, const int32_t* group,
+                      int32_t* winner, int32_t* out, const int32_t* cnt, int which, int small_m, void* stream) {
   COOCC_CHECK_ARG(val && nn && group && winner && out && nc > 0 && K > 0 && ns > 0 && nq > 0, "knn_assign: bad args");
   hipStream_t s = as_stream(stream);
   COOCC_HIP(hipMemsetAsync(winner, 0xFF, sizeof(int32_t) * (size_t)K * nq, s));
   hipLaunchKernelGGL(k_assign_winner, dim3(cdiv((long long)nc * ns, 256)), dim3(256), 0, s, nc, K, ns, nq,
-                     dist_thresh, val, group, winner);
-  hipLaunchKernelGGL(k_assign_lookup, dim3(cdiv((long long)K * nq, 256)), dim3(256), 0, s, K, nq, nn, winner, out);
+                     dist_thresh, val, group, winner, cnt, which, small_m);
+  hipLaunchKernelGGL(k_assign_lookup, dim3(cdiv((long long)K * nq, 256)), dim3(256), 0, s, K, nq, nn, winner, out, cnt, which, small_m);
   COOCC_LAUNCH_CHECK("knn_assign");
   return COOCC_OK;
+}
+
+extern "C" int coocc_knn_assign(int nc, int K, int ns, int nq, float dist_thresh, const float* val,
+                                const int32_t* nn, const int32_t* group, int32_t* winner, int32_t* out,
+                                void* stream) {
+  return knn_assign(nc, K, ns, nq, dist_thresh, val, nn, group, winner, out, nullptr, 0, 0, stream);
+}
+
+// winner: [K][nq_cap] capacity, used as [K][cnt[which]]; out: [K][cnt[which]] dense, as coocc_knn_assign writes it
+extern "C" int coocc_knn_assign_dev(int nc, int K, int ns, int nq_cap, float dist_thresh, const float* val, const int32_t* nn,
+                                    const int32_t* group, int32_t* winner, int32_t* out, const int32_t* cnt, int which, int small_m,
+                                    void* stream) {
+  COOCC_CHECK_ARG(cnt && (unsigned)which < 2u, "knn_assign_dev: bad counts");
+  return knn_assign(nc, K, ns, nq_cap, dist_thresh, val, nn, group, winner, out, cnt, which, small_m, stream);
 }
 
 __global__ void k_knn_threshold(int nq, float thresh, const float* __restrict__ val,
@@ -1031,7 +1157,14 @@ extern "C" int coocc_knn_threshold(int nq, float dist_thresh, const float* val, 
 }
 
 __global__ void k_index_rows(const int32_t* __restrict__ base, int nbase, const int32_t* __restrict__ sel, int n,
-                             int32_t* __restrict__ rows) {
+                             int32_t* __restrict__ rows, const int32_t* __restrict__ cnt, int which_base, int which_n, int k,
+                             int small_m) {
+  if (cnt) {                                   // sel: the [K][n] table's first row; row k starts at k * n, n on the device
+    if (dev_counts_small(cnt, small_m)) return;
+    nbase = cnt[which_base];
+    n = cnt[which_n];
+    sel += (size_t)k * n;
+  }
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int s = sel[i];
@@ -1043,7 +1176,19 @@ extern "C" int coocc_index_rows_i32(const int32_t* base, int nbase, const int32_
                                     void* stream) {
   COOCC_CHECK_ARG(base && sel && rows && nbase > 0 && n >= 0, "index_rows: bad args");
   if (n == 0) return COOCC_OK;
-  hipLaunchKernelGGL(k_index_rows, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), base, nbase, sel, n, rows);
+  hipLaunchKernelGGL(k_index_rows, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), base, nbase, sel, n, rows, (const int32_t*)nullptr, 0,
+                     0, 0, 0);
+  COOCC_LAUNCH_CHECK("k_index_rows");
+  return COOCC_OK;
+}
+
+// rows[i] = base[sel[k][i]] for row k of a dense [K][cnt[which_n]] table `sel`; base has cnt[which_base] entries; n_cap sizes the grid
+extern "C" int coocc_index_rows_i32_dev(const int32_t* base, int which_base, const int32_t* sel, int k, int which_n, int n_cap,
+                                        int32_t* rows, const int32_t* cnt, int small_m, void* stream) {
+  COOCC_CHECK_ARG(base && sel && rows && cnt && n_cap > 0 && k >= 0 && (unsigned)which_base < 2u && (unsigned)which_n < 2u,
+                  "index_rows_dev: bad args");
+  hipLaunchKernelGGL(k_index_rows, dim3(cdiv(n_cap, 256)), dim3(256), 0, as_stream(stream), base, 0, sel, 0, rows, cnt, which_base, which_n, k,
+                     small_m);
   COOCC_LAUNCH_CHECK("k_index_rows");
   return COOCC_OK;
 }

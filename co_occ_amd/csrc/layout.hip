@@ -474,7 +474,12 @@ extern "C" int coocc_compact_flags_ex(const uint8_t* flags, int total, int32_t* 
 }
 
 __global__ void k_lin_to_coords(const int32_t* __restrict__ lin, int n, int X, int Y, int Z,
-                                float* __restrict__ xyz, int64_t* __restrict__ bxyz) {
+                                float* __restrict__ xyz, int64_t* __restrict__ bxyz, const int32_t* __restrict__ cnt, int which,
+                                int small_m) {
+  if (cnt) {                                   // device-count form: n = cnt[which]; nothing is written when a list is "small"
+    if (cnt[0] <= small_m || cnt[1] <= small_m) return;
+    n = min(n, cnt[which]);
+  }
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int l = lin[i];
@@ -489,7 +494,19 @@ extern "C" int coocc_lin_to_coords(const int32_t* lin, int n, int X, int Y, int 
                                    void* stream) {
   COOCC_CHECK_ARG(lin && n >= 0 && X > 0 && Y > 0 && Z > 0, "lin_to_coords: bad args");
   if (n == 0) return COOCC_OK;
-  hipLaunchKernelGGL(k_lin_to_coords, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), lin, n, X, Y, Z, xyz, bxyz);
+  hipLaunchKernelGGL(k_lin_to_coords, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), lin, n, X, Y, Z, xyz, bxyz,
+                     (const int32_t*)nullptr, 0, 0);
+  COOCC_LAUNCH_CHECK("k_lin_to_coords");
+  return COOCC_OK;
+}
+
+// The list length read on the device: lin[0 .. cnt[which]) of at most n_cap entries, cnt = the two list lengths of a one-shot
+// index search (csrc/search.hip); the grid is sized for n_cap.  Nothing is written when cnt[0] <= small_m or cnt[1] <= small_m.
+extern "C" int coocc_lin_to_coords_dev(const int32_t* lin, int n_cap, const int32_t* cnt, int which, int small_m, int X, int Y, int Z,
+                                       float* xyz, void* stream) {
+  COOCC_CHECK_ARG(lin && xyz && cnt && n_cap > 0 && (unsigned)which < 2u && X > 0 && Y > 0 && Z > 0, "lin_to_coords_dev: bad args");
+  hipLaunchKernelGGL(k_lin_to_coords, dim3(cdiv(n_cap, 256)), dim3(256), 0, as_stream(stream), lin, n_cap, X, Y, Z, xyz, (int64_t*)nullptr,
+                     cnt, which, small_m);
   COOCC_LAUNCH_CHECK("k_lin_to_coords");
   return COOCC_OK;
 }

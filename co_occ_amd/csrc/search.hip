@@ -6,14 +6,28 @@
 //
 // Same kernels, same order and same results as co_occ_amd.fuser.BiFuser_N.search (grid forms of top-K / ball query,
 // bucket-pruned FPS); B == 1, both voxel lists longer than fps_num (the reference's other branch, bifuser_n.py:54-60 /
-// 88-94, stays in Python: the call returns COOCC_SEARCH_SMALL and has launched nothing after the count read).
+// 88-94, stays in Python: the call returns COOCC_SEARCH_SMALL and nothing after K1 has written anything but this call's workspace).
+//
+// Two forms.  ONE-SHOT (the default wherever the paired register-resident FPS takes lists of X*Y*Z voxels): right after K1 the
+// 8-byte copy of the counts and its event are enqueued, then EVERY remaining launch, each reading its list lengths from d->counts
+// on the device (grids sized for the capacity V), and only then does the host wait for the counts -- which it needs for nothing
+// but the small-list answer and the caller's bookkeeping.  The stage crosses its hardware queue once: with HIP's four queues a
+// search stream shares an in-order queue with a dense stream, and a second batch of launches issued after the host had seen the
+// counts can queue behind whole dense graphs a second time (single tickets, up to 9 ms; the first crossing is the wait that
+// dominates and stays: profiles/search_oneshot_trace.txt).  HOST-COUNT (large grids, the
+// unpaired fork / join, COOCC_FPS_REG=0, coocc_fuser_search_oneshot(0)): the host waits for the counts after K1 and sizes the
+// remaining launches by them.  Same kernels, same order, same arithmetic, same bits in both.
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "common.h"
 
+// cnt: the stage's two list lengths on the device (one-shot form): nothing is written when one is <= small_m (idx is then stale)
 __global__ __launch_bounds__(256) void k_gather_xyz(const float* __restrict__ xyz, const int32_t* __restrict__ idx, int m,
-                                                     float* __restrict__ out) {
+                                                     float* __restrict__ out, const int32_t* __restrict__ cnt, int small_m) {
+  if (cnt && (cnt[0] <= small_m || cnt[1] <= small_m)) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const int s = idx[i];
@@ -70,6 +84,75 @@ extern "C" size_t coocc_fuser_search_ws(const coocc_search_desc* d) {
     if (rc__ != COOCC_OK) return rc__; \
   } while (0)
 
+// -1: not read yet (COOCC_SEARCH_ONESHOT=0 in the environment switches the one-shot form off), else 0 / 1
+static std::atomic<int> g_oneshot{-1};
+static int oneshot_setting() {
+  int v = g_oneshot.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("COOCC_SEARCH_ONESHOT");
+    v = !(e && e[0] == '0');
+    int expect = -1;
+    if (!g_oneshot.compare_exchange_strong(expect, v)) v = expect;
+  }
+  return v;
+}
+extern "C" int coocc_fuser_search_oneshot(int on) {
+  const int prev = oneshot_setting();
+  if (on >= 0) g_oneshot.store(on ? 1 : 0);
+  return prev;
+}
+
+// 8 pinned bytes per calling thread: the one-shot form's counts land here, so that the copy command is asynchronous to the host
+// whatever memory the caller's counts_host is (a copy into pageable memory may hold the enqueueing thread until it has run --
+// the very wait this form removes).  One call per thread at a time waits for its copy before it returns; never freed.
+static int32_t* pinned_counts() {
+  static thread_local int32_t* p = nullptr;
+  if (!p && hipHostMalloc((void**)&p, 8, hipHostMallocDefault) != hipSuccess) p = nullptr;
+  return p;
+}
+
+// K2-K5 and the row tables of both directions with every list length read from d->counts on the device; all on `stream`, in the
+// order of the paired host-count form below
+static int search_enqueue_dev(const coocc_search_desc* d, const SearchWs& w, int V, void* stream, int sdiag) {
+  const int K = d->K, m = d->fps_num, X = d->X, Y = d->Y, Z = d->Z;
+  const int32_t* cnt = d->counts;                      // [0] = Ni, [1] = Np
+  int32_t* lin_img = d->lin;
+  int32_t* lin_pts = d->lin + V;
+  float* xyz_img = w.xyz;
+  float* xyz_pts = w.xyz + (size_t)V * 3;
+  int32_t* map_img = w.maps;
+  int32_t* map_pts = w.maps + V;
+  SRC(coocc_lin_to_coords_dev(lin_img, V, cnt, 0, m, X, Y, Z, xyz_img, stream));
+  SRC(coocc_lin_to_coords_dev(lin_pts, V, cnt, 1, m, X, Y, Z, xyz_pts, stream));
+  SRC(coocc_voxel_index_map_dev(lin_img, V, cnt, V, map_img, stream));
+  SRC(coocc_voxel_index_map_dev(lin_pts, V, cnt + 1, V, map_pts, stream));
+  if (!(sdiag & 1)) {
+    const int rc = coocc_fps_voxels_pair_dev(lin_pts, 1, w.rep[0], w.fps[0], lin_img, 0, w.rep[1], w.fps[1], w.fps_bytes, V, cnt, m, X, Y, Z, m,
+                                             stream);
+    if (rc == 2) return coocc_set_error(COOCC_EINVAL, "fuser_search: the paired FPS refused a grid it had accepted");
+    SRC(rc);
+  }
+  // one direction: queries (list wq) <- keys (list wk); near: [K][cnt[wq]] key ordinals (-1 = none)
+  auto direction = [&](int dd, const int32_t* lin_q, int wq, const float* xyz_q, const int32_t* map_q, int wk, const float* xyz_k,
+                       const int32_t* map_k, int32_t* near) -> int {
+    if (sdiag & 2) return COOCC_OK;
+    hipLaunchKernelGGL(k_gather_xyz, dim3(cdiv(m, 256)), dim3(256), 0, as_stream(stream), xyz_q, w.rep[dd], m, w.rep_xyz[dd], cnt, m);
+    COOCC_LAUNCH_CHECK("k_gather_xyz");
+    SRC(coocc_knn_topk_voxels_dev(m, K, X, Y, Z, w.rep[dd], lin_q, map_k, d->offsets, d->noff, w.rep_xyz[dd], xyz_k, w.val[dd], w.nn[dd], cnt,
+                                  wk, m, stream));
+    SRC(coocc_ball_query_voxels_dev(m, 0.f, d->radius, d->max_cluster, X, Y, Z, w.rep[dd], lin_q, map_q, w.group[dd], cnt, m, stream));
+    SRC(coocc_knn_assign_dev(m, K, d->max_cluster, V, d->dist_thresh, w.val[dd], w.nn[dd], w.group[dd], w.winner[dd], near, cnt, wq, m, stream));
+    return COOCC_OK;
+  };
+  SRC(direction(1, lin_img, 0, xyz_img, map_img, 1, xyz_pts, map_pts, d->near_pts));
+  for (int k = 0; k < K && !(sdiag & 2); ++k)
+    SRC(coocc_index_rows_i32_dev(K == 1 ? lin_pts : lin_img, K == 1 ? 1 : 0, d->near_pts, k, 0, V, d->rows_p + (size_t)k * V, cnt, m, stream));
+  SRC(direction(0, lin_pts, 1, xyz_pts, map_pts, 0, xyz_img, map_img, d->near_img));
+  for (int k = 0; k < K && !(sdiag & 2); ++k)
+    SRC(coocc_index_rows_i32_dev(lin_img, 0, d->near_img, k, 1, V, d->rows + (size_t)k * V, cnt, m, stream));
+  return COOCC_OK;
+}
+
 extern "C" int coocc_fuser_search(coocc_search_desc* d, void* stream, void* side_stream) {
   COOCC_CHECK_ARG(d && d->cat4 && d->pts && d->lin && d->counts && d->rows && d->rows_p && d->near_img && d->near_pts && d->ws &&
                       d->offsets && d->counts_host, "fuser_search: null pointer");
@@ -91,6 +174,38 @@ extern "C" int coocc_fuser_search(coocc_search_desc* d, void* stream, void* side
   SRC(coocc_fuser_prepare_rows(d->cat4, 1, 4 * C, d->pts, d->pts_rows, d->pts_stride, d->cat4, w.flags, w.flags + V, 1, C, V, stream));
   SRC(coocc_compact_flags(w.flags, V, lin_img, d->counts, w.cws, (size_t)(V / 1024 + 2) * 4, stream));
   SRC(coocc_compact_flags(w.flags + V, V, lin_pts, d->counts + 1, w.cws + (V / 1024 + 2), (size_t)(V / 1024 + 2) * 4, stream));
+  // one-shot: only where the paired register-resident FPS takes this grid's longest possible list (decided on the host at n = V,
+  // before anything after K1 is enqueued) and fps_num keys are enough for top-K
+  if (oneshot_setting() && d->fps_num >= K && coocc_fps_voxels_pair_ok(V, d->X, d->Y, d->Z)) {
+    const bool read = !((sdiag & 4) && d->counts_host[0] > 0);
+    volatile int32_t* pin = read ? pinned_counts() : nullptr;
+    if (read && !pin) return coocc_set_error(COOCC_ENOMEM, "fuser_search: no pinned host memory for the voxel counts");
+    hipEvent_t got = nullptr;
+    if (read) {
+      static const bool fence = [] { const char* e = getenv("COOCC_SEARCH_COUNT_FENCE"); return e && e[0] == '1'; }();
+      pin[0] = pin[1] = -1;                            // counts are >= 0: "not arrived"
+      COOCC_HIP(hipMemcpyAsync((void*)pin, d->counts, 8, hipMemcpyDeviceToHost, s0));
+      COOCC_HIP(hipEventCreateWithFlags(&got, hipEventBlockingSync | hipEventDisableTiming | (fence ? 0u : hipEventDisableSystemFence)));
+      if (hipEventRecord(got, s0) != hipSuccess) {
+        (void)hipEventDestroy(got);
+        return coocc_set_error(COOCC_EHIP, "fuser_search: recording the count event failed");
+      }
+    }
+    const int rc = search_enqueue_dev(d, w, V, stream, sdiag);
+    if (read) {
+      // the stage's one host wait, now behind everything it enqueues (the blocking, fence-less event of the host-count form below)
+      const hipError_t e2 = hipEventSynchronize(got);
+      (void)hipEventDestroy(got);
+      if (e2 != hipSuccess) return coocc_set_error(COOCC_EHIP, "fuser_search: waiting for the voxel counts failed: %s", hipGetErrorString(e2));
+      if (pin[0] < 0 || pin[1] < 0) {                  // the copy command is complete when its event fires; never seen otherwise
+        COOCC_HIP(hipStreamSynchronize(s0));
+        if (pin[0] < 0 || pin[1] < 0) return coocc_set_error(COOCC_EHIP, "fuser_search: the voxel counts did not reach the host");
+      }
+      d->counts_host[0] = pin[0]; d->counts_host[1] = pin[1];
+    }
+    if (rc != COOCC_OK) return rc;
+    return (d->counts_host[0] <= d->fps_num || d->counts_host[1] <= d->fps_num) ? COOCC_SEARCH_SMALL : COOCC_OK;
+  }
   if (!((sdiag & 4) && d->counts_host[0] > 0)) COOCC_HIP(hipMemcpyAsync(d->counts_host, d->counts, 8, hipMemcpyDeviceToHost, s0));
   if (!((sdiag & 4) && d->counts_host[0] > 0)) {
     // the one host sync of the stage.  A BLOCKING event: the calling thread sleeps instead of spinning (hipStreamSynchronize may
@@ -167,7 +282,8 @@ extern "C" int coocc_fuser_search(coocc_search_desc* d, void* stream, void* side
                        const float* xyz_k, const int32_t* map_k, int32_t* near) -> int {
     if (sdiag & 2) return COOCC_OK;
     if (!paired) SRC(coocc_fps_voxels(lin_q, Q, d->X, d->Y, d->Z, d->fps_num, w.rep[dd], w.fps[dd], w.fps_bytes, st));
-    hipLaunchKernelGGL(k_gather_xyz, dim3(cdiv(d->fps_num, 256)), dim3(256), 0, as_stream(st), xyz_q, w.rep[dd], d->fps_num, w.rep_xyz[dd]);
+    hipLaunchKernelGGL(k_gather_xyz, dim3(cdiv(d->fps_num, 256)), dim3(256), 0, as_stream(st), xyz_q, w.rep[dd], d->fps_num, w.rep_xyz[dd],
+                       (const int32_t*)nullptr, 0);
     COOCC_LAUNCH_CHECK("k_gather_xyz");
     SRC(coocc_knn_topk_voxels(d->fps_num, Nk, K, d->X, d->Y, d->Z, w.rep[dd], lin_q, map_k, d->offsets, d->noff, w.rep_xyz[dd], xyz_k,
                               w.val[dd], w.nn[dd], st));

@@ -127,8 +127,11 @@ int coocc_ball_query(int b, int n, int m, float min_radius, float max_radius, in
  * top-K -> ball query -> assignment -> neighbour row tables) as ONE call: every launch, the fork / join of the two directions
  * over `stream` / `side_stream` and the stage's single device->host read (the two counts) are issued from C++ (csrc/search.hip).
  * B == 1; grid small enough for coocc_fps_voxels.  Returns COOCC_OK, COOCC_SEARCH_SMALL (a list has <= fps_num voxels: the
- * reference takes its other branch, bifuser_n.py:54-60 -- nothing was launched after the count read, use the generic entry
- * points), or a negative error.  On return everything is enqueued and `stream` has joined `side_stream`. */
+ * reference takes its other branch, bifuser_n.py:54-60 -- nothing after K1 has written anything but `ws`, use the generic entry
+ * points), or a negative error.  On return everything is enqueued and `stream` has joined `side_stream`.
+ * One-shot form (default where coocc_fps_voxels_pair_ok(X*Y*Z, X, Y, Z) and fps_num >= K): everything after K1 reads its list
+ * lengths from `counts` on the device and is enqueued BEFORE the host waits for the counts, all on `stream`; same kernels, order
+ * and bits as the host-count form, which large grids and coocc_fuser_search_oneshot(0) keep. */
 #define COOCC_SEARCH_SMALL 1
 typedef struct coocc_search_desc {
   float* cat4;             /* [V,4C] concat rows; slot 0 (camera rows) already written, slots 1..3 written here / by G1 */
@@ -151,6 +154,34 @@ typedef struct coocc_search_desc {
 } coocc_search_desc;
 size_t coocc_fuser_search_ws(const coocc_search_desc* d);
 int coocc_fuser_search(coocc_search_desc* d, void* stream, void* side_stream);
+/* on = 0 / 1: switch the one-shot form off / on for the whole process (COOCC_SEARCH_ONESHOT=0 in the environment: off from the
+ * start); on < 0: query only.  Returns the previous setting. */
+int coocc_fuser_search_oneshot(int on);
+
+/* ---- Device-count forms of K2..K5 for the one-shot search: `cnt` = the stage's two list lengths on the device (img, pts);
+ * cnt[which] is the length a launch works on, grids are sized for the capacity and surplus threads leave at once; the [K][Q]
+ * tables keep their count-dependent strides.  When cnt[0] <= small_m or cnt[1] <= small_m (the reference's small-list branch,
+ * small_m = fps_num) every one of them returns without writing.  Otherwise the bits of the host-count entry points. */
+int coocc_lin_to_coords_dev(const int32_t* lin, int n_cap, const int32_t* cnt, int which, int small_m, int X, int Y, int Z,
+                            float* xyz, void* stream);
+/* 1 when coocc_fps_voxels_pair takes lists of up to n voxels on this grid (n is the hardest length up to n), else 0; host only */
+int coocc_fps_voxels_pair_ok(int n, int X, int Y, int Z);
+int coocc_fps_voxels_pair_dev(const int32_t* lin0, int which0, int32_t* idx0, void* ws0, const int32_t* lin1, int which1,
+                              int32_t* idx1, void* ws1, size_t ws_bytes_each, int n_cap, const int32_t* cnt, int small_m,
+                              int X, int Y, int Z, int m, void* stream);
+int coocc_knn_topk_voxels_dev(int nq, int K, int X, int Y, int Z, const int32_t* rep_ord, const int32_t* lin_q,
+                              const int32_t* map_k, const uint32_t* offsets, int noff, const float* q, const float* key,
+                              float* val, int32_t* idx, const int32_t* cnt, int which, int small_m, void* stream);
+int coocc_ball_query_voxels_dev(int m, float min_radius, float max_radius, int nsample, int X, int Y, int Z,
+                                const int32_t* centre_ord, const int32_t* lin_q, const int32_t* map_q, int32_t* idx,
+                                const int32_t* cnt, int small_m, void* stream);
+/* winner:[K][nq_cap] scratch used as [K][cnt[which]]; out:[K][cnt[which]] dense */
+int coocc_knn_assign_dev(int nc, int K, int ns, int nq_cap, float dist_thresh, const float* val, const int32_t* nn,
+                         const int32_t* group, int32_t* winner, int32_t* out, const int32_t* cnt, int which, int small_m,
+                         void* stream);
+/* rows[i] = base[sel[k][i]], sel a dense [K][cnt[which_n]] table, base of cnt[which_base] entries (coocc_index_rows_i32's rules) */
+int coocc_index_rows_i32_dev(const int32_t* base, int which_base, const int32_t* sel, int k, int which_n, int n_cap,
+                             int32_t* rows, const int32_t* cnt, int small_m, void* stream);
 
 /* map[v] = ordinal of voxel v in lin[0..n) or -1.  map:[nvox] i32. */
 int coocc_voxel_index_map(const int32_t* lin, int n, int nvox, int32_t* map, void* stream);

@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+from co_occ_amd import streams  # noqa: E402
 
 
 def main():
@@ -31,7 +32,7 @@ def main():
     torch.cuda.synchronize()
     gp.trace.clear()
     gp.dense_ev.clear()
-    base = torch.cuda.Event(enable_timing=True)
+    base = streams.new_event(timing=True)      # the type of Ticket.events / dense_ev: elapsed_time() needs both ends alike
     base.record()
     base.synchronize()
     h0 = time.perf_counter()
