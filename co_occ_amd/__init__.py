@@ -33,6 +33,7 @@ from .evaluation import SemanticEvaluator, cm_to_ious, evaluation_semantic
 from . import optim
 from . import occ_gt
 from . import sweeps
+from . import visualize
 
 register_into_mmdet()
 

@@ -240,6 +240,8 @@ SIGNATURES = {
     "coocc_occ_cloud_aabb": (I, [P, L, I, P, P, P, P]),
     "coocc_sweeps_merge_ws": (Z, [L]),
     "coocc_sweeps_merge": (I, [P, L, I, P, P, I, P, I, F, P, L, P, P, Z, P]),
+    "coocc_occ_view_prepare": (L, [P, I, I, I, I, P, P, Z, P]),
+    "coocc_occ_view_cast": (I, [P, P, I, I, I, P, P, I, I, I, I, I, I, P, Z, P, P, P, P, P, P]),
 }
 
 _lib = None

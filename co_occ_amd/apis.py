@@ -116,6 +116,27 @@ def save_rendered_panels(result_or_maps, out_dir, gt_img=None, prefix="view_"):
     return paths, panels
 
 
+def visualize_result(img_inputs, output_voxels, img_canvas=None, cat_save_file=None, save_folder=None, vox_origin=None, voxel_size=None):
+    """The picture of ``visualize_nusc.py`` straight from a ``simple_test`` / ``pipelined_test`` result, without the pickle of
+    ``save_output_nuscenes``: ``img_inputs`` gives ``cam2lidar`` as there (``rots``, ``trans`` of its entries 1 and 2),
+    ``output_voxels`` is any label volume [1,X,Y,Z] or [X,Y,Z] -- ``predict_labels``' uint8, upstream's int64 argmax, or a ground-truth
+    volume of ``occ_gt`` -- and stays on the device.  ``img_canvas``: the six 480 x 270 input frames (PIL images or uint8 arrays);
+    without it their boxes stay black.  ``vox_origin`` / ``voxel_size`` default to the reference's nuScenes range divided by the
+    volume's own shape.  Returns the canvas (uint8 [1640,2930,3]); writes ``cat_save_file`` and, into ``save_folder``, the eight
+    views when given (``visualize.draw_nusc_occupancy``)."""
+    from . import visualize as VZ
+    rots, trans = img_inputs[1:3]
+    cam2lidar = np.repeat(np.eye(4)[np.newaxis], repeats=rots.shape[1], axis=0)
+    cam2lidar[:, :3, :3] = rots[0].detach().cpu().numpy()
+    cam2lidar[:, :3, -1] = trans[0].detach().cpu().numpy()
+    vol = output_voxels[0] if output_voxels.ndim == 4 else output_voxels
+    if vox_origin is None or voxel_size is None:
+        o, v = VZ.grid_of(list(vol.shape))
+        vox_origin, voxel_size = (o if vox_origin is None else vox_origin), (v if voxel_size is None else voxel_size)
+    return VZ.draw_nusc_occupancy(img_canvas, vol, vox_origin, voxel_size, grid=np.array(vol.shape), save_folder=save_folder,
+                                  cat_save_file=cat_save_file, cam2lidar=cam2lidar)
+
+
 def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=None):
     """The loop of ``custom_single_gpu_test`` (P/coocc/apis/test.py:43-45: ``result = model(return_loss=False, **data)`` once per
     sample) with ``slots`` samples in flight (``co_occ_amd.serving``): a generator of ``(data, result)`` in sample order, ``result``

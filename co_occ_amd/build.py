@@ -27,9 +27,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # sweeps.hip: the sweep transform restates numpy's float64 xyz @ R.T and + t with a rounding to fp32 after each -- every product
 # rounded in fp64, sums left to right; a contracted multiply-add moves a coordinate that sits near an fp32 rounding boundary
 # (DESIGN.md 18).
+# occ_views.hip: which face of which cube a sample sees is decided by comparing fp32 slab distances that tests/occ_view_refs.py
+# restates in numpy one rounded operation at a time; a contracted (lo - e) * inv or fwd + u * R changes the winner of a near-tie
+# (DESIGN.md 19).
 FILE_FLAGS = {"fine_fused.hip": ["-fno-slp-vectorize"], "lidarseg.hip": ["-ffp-contract=off"],
               "render_eval.hip": ["-ffp-contract=off"], "depth_maps.hip": ["-ffp-contract=off"], "occ_gt.hip": ["-ffp-contract=off"],
-              "sweeps.hip": ["-ffp-contract=off"]}
+              "sweeps.hip": ["-ffp-contract=off"], "occ_views.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -1255,6 +1255,40 @@ int coocc_sweeps_merge(const float* raw, int64_t in_rows, int load_dim, const co
                        int nseg, const int32_t* use_dim_host, int n_use, float radius, float* out, int64_t out_rows, int32_t* count,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- occupancy pictures (co_occ_amd/visualize.py, csrc/occ_views.hip): the cubes of the reference's
+ * draw_nusc_occupancy (P/visualize/visualize_nusc.py) ray-cast on the device instead of drawn by mayavi.
+ *
+ * occ_view_prepare: labels [X][Y][Z], uint8 or (labels_i64) int64 of which the low byte counts -> draw uint8 [X][Y][Z] (17 becomes 20,
+ *   then the ego-car block of labels 17 / 18 / 19 over the centre; a voxel is drawn iff 0 < v < 20) and masks: uint16 [X][Y][zw]
+ *   column words (zw = ceil(Z / 16), bit k & 15 of word k >> 4) followed, at the next multiple of 16 bytes, by uint8
+ *   [ceil(X/8)][ceil(Y/8)][zw] brick flags.  X, Y >= 12, Z >= 10 (the block must fit), each <= 4096, X * Y * Z < 2^31.  With masks ==
+ *   NULL nothing runs and the size of masks in bytes is returned.  One launch, no atomics, no host read. */
+int64_t coocc_occ_view_prepare(const void* labels, int labels_i64, int X, int Y, int Z, uint8_t* draw, void* masks, size_t masks_bytes,
+                               void* stream);
+/* occ_view_cast: rgb uint8 [V][H][W][3] of V <= 8 views of one frame size, S x S samples a pixel (S <= 8), one launch.
+ *   grid_host   fp32 [7]: origin[3], voxel_size[3], half cube edge; cube (i, j, k) spans centre -+ half per axis with centre =
+ *               origin + ((float)index + 0.5f) * voxel_size; 2 * half may not exceed the smallest voxel side
+ *   views_host  fp32 [V][16]: eye[3], fwd[3], R[3] (right * tan_x), U[3] (up * tan_y), near, far, col0, 0.  The frame is FH x FW pixels
+ *               and the view writes its columns col0 .. col0 + W - 1 (H <= FH rows from the top)
+ *   palette_host uint8 [19][3]; colour row = draw value - 1
+ *   Sample (gx, gy) of the FW*S x FH*S sample frame: u = (float)(2 gx + 1 - FW S) * (float)(1 / (FW S)), v = (float)(FH S - 2 gy - 1) *
+ *   (float)(1 / (FH S)), d = (fwd + u R) + v U, every product rounded.  An axis with |d| < 1e-30 is decided by containment of the eye
+ *   in the cube's interval; on the others ta = (lo - e) * inv, tb = (hi - e) * inv with inv = 1 / d (IEEE), entry = max of min(ta, tb)
+ *   (lowest axis among equals), exit = min of max(ta, tb) (likewise); a cube is hit when entry <= exit, at t = entry when entry >=
+ *   near, else at t = exit when exit >= near; hits with t > far are dropped; among cubes the smallest t wins, then the lowest linear
+ *   voxel index.  Faces: 0 +x, 1 -x, 2 +y, 3 -y, 4 +z, 5 -z, shades 208 208 168 168 256 128; a sample's colour is (palette * shade +
+ *   128) >> 8, 255 without a hit; a pixel is (sum + S*S/2) / (S*S) of its samples.
+ *   ids int32 / faces uint8 / t fp32 [V][H*S][W*S], all three or none: per sample the voxel's linear index (-1 for none), the face
+ *   (255) and t (+inf).
+ *   reads uint32 [V][H*S][W*S][2], optional and only with ids: how many brick flags and how many column words the sample's walk read.
+ *   lds_budget_bytes: 0 for the default, 16 KiB; at most 80 KiB counts.  When both masks fit the budget they are staged in LDS
+ *   (returns 0); otherwise only the brick flags are (at most 16 KiB of them) and the column words are read from memory (returns 1).
+ *   Masks above 16 KiB hold a CU to two workgroups, which measured slower than reading the words from memory (200 x 200 x 16:
+ *   DESIGN.md 19), hence the default.  Same bits either way, and from run to run: no atomics. */
+int coocc_occ_view_cast(const uint8_t* draw, const void* masks, int X, int Y, int Z, const float* grid_host, const float* views_host, int V,
+                        int H, int W, int S, int FW, int FH, const uint8_t* palette_host, size_t lds_budget_bytes, uint8_t* rgb,
+                        int32_t* ids, uint8_t* faces, float* t, uint32_t* reads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
