@@ -38,6 +38,13 @@ class SearchDesc(ctypes.Structure):
                [("ws_bytes", ctypes.c_size_t), ("counts_host", c_void_p)]
 
 
+class CopyItem(ctypes.Structure):
+    """struct coocc_copy_item (include/coocc_hip.h)."""
+    _fields_ = [("dst", c_void_p), ("src", c_void_p), ("bytes", ctypes.c_size_t)]
+
+
+COPY_MANY_MAX = 16      # COOCC_COPY_MANY_MAX
+
 P, I, F, Z, L = c_void_p, c_int, c_float, c_size_t, c_int64
 # name -> (restype, argtypes); mirrors include/coocc_hip.h one to one (checked by tests/test_abi.py)
 SIGNATURES = {
@@ -67,6 +74,7 @@ SIGNATURES = {
     "coocc_compact_flags": (I, [P, I, P, P, P, Z, P]),
     "coocc_compact_flags_ex": (I, [P, I, P, P, P, P, Z, P]),
     "coocc_lin_to_coords": (I, [P, I, I, I, I, P, P, P]),
+    "coocc_copy_many": (I, [P, I, P]),
     "coocc_furthest_point_sampling": (I, [I, I, I, P, P, P, P]),
     "coocc_fps_voxels_ws": (Z, [I, I, I]),
     "coocc_fps_voxels": (I, [P, I, I, I, I, I, P, P, Z, P]),

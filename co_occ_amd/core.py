@@ -461,11 +461,32 @@ ZSHARE = __import__("os").environ.get("COOCC_BF16_ZSHARE", "1") != "0"       # r
 # / bf16 operand rows, arrival counters, amax words, pooling / FPS / voxelisation workspaces.  One dict, so that a captured graph
 # can pin everything its stream owns (``stream_scratch``) without knowing who allocated what.
 _stream_bufs = {}
+_scratch_ns = __import__("threading").local()
+
+
+class scratch_space:
+    """``with scratch_space("search3:"):`` -- every ``stream_buffer`` the calling THREAD asks for inside gets ``name`` in front of
+    its kind, i.e. a registry entry of its own.  For work that shares a stream with launches it is not ordered against on the host:
+    the serving loop's search stage runs on its slot's dense stream from a helper thread while the issuing thread replays another
+    slot's graph (or runs its eager dense stage) on the same stream, so a kind used on both sides (the LiDAR producer's
+    convolutions use the dense stage's Winograd / split-K scratch) could be rewritten between two launches of one of them."""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __enter__(self):
+        self.prev = getattr(_scratch_ns, "name", "")
+        _scratch_ns.name = self.name
+        return self
+
+    def __exit__(self, *exc):
+        _scratch_ns.name = self.prev
 
 
 def stream_buffer(device, kind, n, dtype=_F32, zero=False):
     """The buffer ``kind`` of ``device``'s current stream with at least ``n`` elements.  A buffer that is too small is REPLACED by a
     fresh one (zeros when ``zero``, else uninitialised) -- the old tensor lives on only where someone holds it (a captured graph)."""
+    kind = getattr(_scratch_ns, "name", "") + kind
     key = (device.index, _lib.stream(device).value or 0, kind)      # a NULL c_void_p reads back as None: the default stream is 0
     t = _stream_bufs.get(key)
     if t is None or t.numel() < n:

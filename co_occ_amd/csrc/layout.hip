@@ -511,6 +511,81 @@ extern "C" int coocc_lin_to_coords_dev(const int32_t* lin, int n_cap, const int3
   return COOCC_OK;
 }
 
+// ------------------------------------------------------------------ many small copies, one launch
+// A new frame's dense-stage inputs reach their slot as 14 device -> device copies: 8.6 MB of image features beside camera matrices of
+// 36-156 bytes, each a launch of ~8 us on the lane its search and its dense stage run on.  coocc_copy_many moves up to
+// COOCC_COPY_MANY_MAX contiguous buffers with ONE launch.  The table travels by value in the kernel arguments: no allocation, no host
+// synchronisation, no memcpy node -- a caller may capture it.  Blocks are dealt over the items in proportion to their size, one block
+// per COPY_CHUNK bytes (more per block above COPY_MAX_BLOCKS blocks), so a block works on one contiguous byte range of one item.
+// A range whose two addresses are 16-byte aligned moves as 16-byte vectors; the rest of it (and the whole range when both addresses
+// are only 4-byte aligned) as 4-byte words; what is left as bytes.  Plain vector loads and stores.
+constexpr int COPY_THREADS = 256;
+constexpr unsigned long long COPY_CHUNK = 16384;       // 256 threads x 4 x 16 bytes; ranges start on multiples of it
+constexpr unsigned long long COPY_MAX_BLOCKS = 4096;
+
+struct CopyTable {
+  char* dst[COOCC_COPY_MANY_MAX];
+  const char* src[COOCC_COPY_MANY_MAX];
+  unsigned long long bytes[COOCC_COPY_MANY_MAX];
+  unsigned first[COOCC_COPY_MANY_MAX + 1];     // first[i] .. first[i+1]: the blocks of item i
+  unsigned long long chunk;                    // bytes per block, a multiple of COPY_CHUNK
+  int n;
+};
+
+__global__ __launch_bounds__(COPY_THREADS) void k_copy_many(const CopyTable t) {
+  const unsigned b = blockIdx.x;
+  int i = 0;
+#pragma unroll
+  for (int k = 1; k < COOCC_COPY_MANY_MAX; ++k)
+    if (k < t.n && b >= t.first[k]) i = k;       // first[] does not decrease: the last item whose range starts at or before b
+  const unsigned long long off = (unsigned long long)(b - t.first[i]) * t.chunk;
+  const unsigned long long total = t.bytes[i];
+  if (off >= total) return;
+  const unsigned long long len = total - off < t.chunk ? total - off : t.chunk;
+  char* d = t.dst[i] + off;
+  const char* s = t.src[i] + off;
+  const uintptr_t al = (uintptr_t)d | (uintptr_t)s;
+  unsigned long long done = 0;
+  if ((al & 15) == 0) {
+    const unsigned long long nv = len >> 4;
+    for (unsigned long long v = threadIdx.x; v < nv; v += COPY_THREADS) ((uint4*)d)[v] = ((const uint4*)s)[v];
+    done = nv << 4;
+  }
+  if ((al & 3) == 0) {
+    const unsigned long long nw = (len - done) >> 2;
+    for (unsigned long long w = threadIdx.x; w < nw; w += COPY_THREADS) ((uint32_t*)(d + done))[w] = ((const uint32_t*)(s + done))[w];
+    done += nw << 2;
+  }
+  for (unsigned long long k = done + threadIdx.x; k < len; k += COPY_THREADS) d[k] = s[k];
+}
+
+extern "C" int coocc_copy_many(const coocc_copy_item* items, int n, void* stream) {
+  COOCC_CHECK_ARG(items && n >= 1 && n <= COOCC_COPY_MANY_MAX, "copy_many: 1 .. %d items per call", COOCC_COPY_MANY_MAX);
+  CopyTable t;
+  unsigned long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    COOCC_CHECK_ARG(items[i].bytes == 0 || (items[i].dst && items[i].src), "copy_many: null pointer in item %d", i);
+    total += items[i].bytes;
+  }
+  if (total == 0) return COOCC_OK;
+  t.chunk = COPY_CHUNK * ((total / COPY_MAX_BLOCKS + COPY_CHUNK - 1) / COPY_CHUNK);
+  if (t.chunk < COPY_CHUNK) t.chunk = COPY_CHUNK;
+  unsigned nblk = 0;
+  for (int i = 0; i < COOCC_COPY_MANY_MAX; ++i) {
+    const bool on = i < n;
+    t.dst[i] = on ? (char*)items[i].dst : nullptr;
+    t.src[i] = on ? (const char*)items[i].src : nullptr;
+    t.bytes[i] = on ? (unsigned long long)items[i].bytes : 0ull;
+    t.first[i] = nblk;
+    nblk += (unsigned)((t.bytes[i] + t.chunk - 1) / t.chunk);      // <= COPY_MAX_BLOCKS + n in all
+  }
+  t.first[COOCC_COPY_MANY_MAX] = nblk;
+  t.n = n;
+  hipLaunchKernelGGL(k_copy_many, dim3(nblk), dim3(COPY_THREADS), 0, as_stream(stream), t);
+  COOCC_LAUNCH_CHECK("k_copy_many");
+  return COOCC_OK;
+}
+
 // ------------------------------------------------------------------ CU-partitioned streams
 // The FPS chains are latency-bound single workgroups; sharing a CU with convolution waves doubles
 // their time (measured).  hipExtStreamCreateWithCUMask gives them private CUs: one stream restricted

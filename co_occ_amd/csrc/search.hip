@@ -158,8 +158,11 @@ extern "C" int coocc_fuser_search(coocc_search_desc* d, void* stream, void* side
                       d->offsets && d->counts_host, "fuser_search: null pointer");
   COOCC_CHECK_ARG(d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0 && d->K >= 1 && d->K <= 8 && d->fps_num > 0 && d->max_cluster > 0 &&
                       d->noff > 0, "fuser_search: bad sizes");
-  COOCC_CHECK_ARG(stream != side_stream && side_stream, "fuser_search: needs a second stream for the img <- pts direction");
   const int V = d->X * d->Y * d->Z, K = d->K, C = d->C;
+  // the second stream carries the img <- pts direction of the UNPAIRED form only (large grids): where the paired FPS takes this
+  // grid's longest list both directions run on `stream` and a caller need not own one (side_stream = NULL)
+  COOCC_CHECK_ARG(side_stream ? stream != side_stream : coocc_fps_voxels_pair_ok(V, d->X, d->Y, d->Z) == 1,
+                  "fuser_search: needs a second stream for the img <- pts direction");
   SearchWs w = carve((char*)d->ws, V, K, d->fps_num, d->max_cluster, d->X, d->Y, d->Z);
   COOCC_CHECK_ARG(d->ws_bytes >= w.total, "fuser_search: workspace smaller than coocc_fuser_search_ws()");
   hipStream_t s0 = as_stream(stream), s1 = as_stream(side_stream);
@@ -271,6 +274,7 @@ extern "C" int coocc_fuser_search(coocc_search_desc* d, void* stream, void* side
   // wait per sample, profiles/r6_serving_probe_events.txt).  Both directions then run on `stream`, one after the other (+ ~0.2 ms of
   // search latency, which is prefetched).  Unpaired (large grids): each direction's own FPS chain runs on its stream, forked first.
   void* side_q = paired ? stream : side_stream;
+  if (!paired && !side_stream) return finish(coocc_set_error(COOCC_EINVAL, "fuser_search: needs a second stream for the img <- pts direction"));
   if (!paired) {
     if (hipEventRecord(fork, s0) != hipSuccess || hipStreamWaitEvent(s1, fork, 0) != hipSuccess)
       return finish(coocc_set_error(COOCC_EHIP, "fuser_search: forking the side stream failed"));

@@ -461,8 +461,10 @@ class BiFuser_N(nn.Module):
             keep = pts_voxel_feats.float().contiguous()
             d.pts, d.pts_rows, d.pts_stride = keep.data_ptr(), 0, 0
         cur = torch.cuda.current_stream(dev)
-        side = _side_stream(dev, cur)
-        rc = _lib.load().coocc_fuser_search(ctypes.byref(d), ctypes.c_void_p(cur.cuda_stream), ctypes.c_void_p(side.cuda_stream))
+        # the paired FPS runs both directions on `cur`: a second stream is created only for a grid that takes the unpaired fork / join
+        lib = _lib.load()
+        side = None if lib.coocc_fps_voxels_pair_ok(slot.V, X, Y, Z) == 1 else _side_stream(dev, cur).cuda_stream
+        rc = lib.coocc_fuser_search(ctypes.byref(d), ctypes.c_void_p(cur.cuda_stream), ctypes.c_void_p(side))
         if rc == 1:           # COOCC_SEARCH_SMALL: the reference's other branch
             return self.search(slot.img_rows().as_ncdhw(), pts_voxel_feats, slot=slot)
         _lib.check(rc)

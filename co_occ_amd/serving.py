@@ -8,9 +8,12 @@ reference's call):
 * a frame is bound to one of ``slots`` sample slots.  The slot's ``SearchSlot`` (concat rows, voxel lists, device-side counts,
   neighbour tables) and the few inputs the DENSE stage reads (2-D image features, camera matrices) sit at fixed addresses;
   ``submit(frame)`` COPIES the new frame's tensors there -- there is no per-frame capture;
-* pooling (fused Lift (x) Splat) + the index search (K1-K5, one C-ABI call, ``coocc_fuser_search``) run EAGERLY on the slot's
-  prefetch stream from a helper thread -- they read the frame's own tensors, have one device->host read, and are
-  latency-bound on two CUs, hidden under the dense stages of earlier frames;
+* the search stage -- that copy (one launch, ``coocc_copy_many``), pooling (fused Lift (x) Splat) and the index search (K1-K5, one
+  C-ABI call, ``coocc_fuser_search``) -- is issued EAGERLY from a helper thread: it reads the frame's own tensors, has one
+  device->host read, and is latency-bound on two CUs, hidden under the dense stages of the other lanes.  It runs on the slot's
+  DENSE stream (the lane form, the default): between the slot's previous replay and its own, both on that stream, so the stream's
+  order is all the ordering it needs and the loop owns ``dense_streams`` streams in all -- no more than the four hardware queues
+  a process gets by default.  ``search_lanes=False`` gives every slot a search stream of its own instead (16 queues and more);
 * the dense stage (G1 -> con_enc -> CustomResNet3D -> FPN3D -> OccHead coarse + fine -> render) is the slot's captured
   ``DenseGraph``: one launch on one of ``dense_streams`` streams.  A frame whose LiDAR sweep is denser than the captured
   capacity takes the eager dense stage (``eager_fallbacks``).
@@ -20,6 +23,7 @@ reference's call):
 bit-identical to sequential eager calls (tests/test_gpu_serving.py).
 """
 import collections
+import ctypes
 import os
 import threading
 import time
@@ -27,7 +31,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
-from . import core, graph as cg, streams as cstreams_
+from . import _lib, core, graph as cg, streams as cstreams_
 
 CAM_KEYS = ("rots", "trans", "intrins", "post_rots", "post_trans", "bda")
 
@@ -72,6 +76,10 @@ class Ticket:
 # dense-stage inputs into the slot, 2: the pooling (fused lift-splat), 4: the index search (K1-K5).  The outputs are then NOT the frame's.
 _DIAG_SKIP = int(os.environ.get("COOCC_SERVING_DIAG_SKIP", "0"))
 SLOT_WAIT_HOST = os.environ.get("COOCC_SLOT_WAIT", "host") != "device"     # see ServingPipeline._search
+# what ``ServingPipeline(search_lanes=None)`` means: 1 (default) the search stage runs on its slot's dense stream, 0 on a stream of its
+# own per slot (for a process with many hardware queues, and for A/B runs of an unchanged bench.py)
+SEARCH_LANES = os.environ.get("COOCC_SEARCH_LANES", "1") != "0"
+COPY_MANY = os.environ.get("COOCC_COPY_MANY", "1") != "0"      # 0: one copy_ per tensor in ServingPipeline._copy_in (launch-count A/B)
 
 
 def _clone_frame_item(v):
@@ -89,7 +97,7 @@ class ServingPipeline:
     a frame's dense stage has been issued (bench.py issues its RCCL all-gather there)."""
 
     def __init__(self, model, example, slots=6, dense_streams=3, ahead=0, render=None, search_priority=0, after_replay=None,
-                 time_dense=False, after_done=None):
+                 time_dense=False, after_done=None, search_lanes=None):
         assert not model.training, "ServingPipeline serves the eval-mode (folded-BN) path"
         self.model = model
         pts = example.get("pts")
@@ -105,14 +113,25 @@ class ServingPipeline:
         # searches in flight ahead of the dense stage: at most slots - dense streams (a slot is rewritten only after the replay
         # that read it finished); `ahead` limits it further (concurrent searches contend with each other and with the graphs)
         most = max(1, n - self.ndense) if n > 1 else 1
-        self.ahead = most if ahead <= 0 else max(1, min(int(ahead), most))
+        self.lanes = SEARCH_LANES if search_lanes is None else bool(search_lanes)
+        # lanes (below): ONE by default.  A lane runs its search and its replay one after the other, so a search is hidden only under
+        # the OTHER lanes' replays, i.e. only while the lanes are out of phase; with `most` searches dispatched together the lanes
+        # fall into step -- three searches side by side on an otherwise idle device, then three replays contending -- and stay there
+        # (263-277 samples/s).  One search at a time staggers them: 296-298 against the parent's 258-277 (profiles/search_lanes_ab.txt)
+        self.ahead = (1 if self.lanes else most) if ahead <= 0 else max(1, min(int(ahead), most))
         self.after_replay, self.after_done, self.time_dense = after_replay, after_done, time_dense
         # (CU-masked streams -- the FPS chains on reserved CUs, the dense graphs masked away from them -- were built and measured in
         # round 6: 270 -> 44-64 samples/s, profiles/r6_reserve_cus_*.txt; removed.)
         self.dense_streams = [torch.cuda.Stream(device=dev) for _ in range(self.ndense)]
-        self.search_streams = [torch.cuda.Stream(device=dev, priority=search_priority) for _ in range(n)]
+        # LANES (the default): slot k's search stage -- copies, pooling, index search -- is issued on dense stream k % ndense, the
+        # stream of the two replays it has to sit between (the slot's previous one and its own), so the stream's order is all the
+        # ordering there is and `ndense` lanes + the default stream are all the streams the loop uses: with the four hardware
+        # queues a process gets by default nothing shares a queue (profiles/search_lanes_*.txt).  search_lanes=False:
+        # one search stream per slot next to the dense streams, ordered by events (more queues than streams: 16 and up).
+        self.search_streams = None if self.lanes else [torch.cuda.Stream(device=dev, priority=search_priority) for _ in range(n)]
         self.slots = [cg.make_slot(model, self.grid, dev) for _ in range(n)]
         self.static = [self._make_static(example) for _ in range(n)]
+        self._copy_tables = [None] * n
         self.slot_done = [None] * n            # event: the last replay that read slot k
         self.graphs = [None] * n
         self.tpool = ThreadPoolExecutor(self.ahead)
@@ -153,17 +172,38 @@ class ServingPipeline:
         return st
 
     def _copy_in(self, k, fr):
-        """The new frame's dense-stage inputs -> slot k's static tensors (on the current = the slot's prefetch stream)."""
+        """The new frame's dense-stage inputs -> slot k's static tensors (on the current stream: the slot's lane / search stream)."""
         st = self.static[k]
-        st["img_feats"][0].copy_(fr["img_feats"][0], non_blocking=True)
+        pairs = [(st["img_feats"][0], fr["img_feats"][0])]
         if st["cams"] is not None:
-            for d, s in zip(st["cams"], fr["cams"]):
-                d.copy_(s, non_blocking=True)
-        for d, s in zip(st["transform"][:-1], fr["transform"][:-1]):
-            if torch.is_tensor(d):
-                d.copy_(s, non_blocking=True)
+            pairs += zip(st["cams"], fr["cams"])
+        pairs += [(d, s) for d, s in zip(st["transform"][:-1], fr["transform"][:-1]) if torch.is_tensor(d)]
         if st["gemo"] is not None:
-            st["gemo"].copy_(fr["gemo"], non_blocking=True)
+            pairs.append((st["gemo"], fr["gemo"]))
+        # one launch for all of them (coocc_copy_many, csrc/layout.hip): the table of the slot is built once -- the destinations
+        # are static -- and only the sources change per frame.  A source that is not a contiguous device tensor of the
+        # destination's type and shape goes through copy_ (which converts / gathers / uploads).
+        tab = self._copy_tables[k]
+        if tab is None:
+            tab = self._copy_tables[k] = (_lib.CopyItem * len(pairs))()
+            for it, (d, _) in zip(tab, pairs):
+                it.dst, it.bytes = d.data_ptr(), d.numel() * d.element_size()
+        direct = [COPY_MANY and torch.is_tensor(s) and s.device == d.device and s.dtype == d.dtype and s.shape == d.shape
+                  and s.is_contiguous() and d.is_contiguous() for d, s in pairs]
+        if not all(direct):
+            for (d, s), ok in zip(pairs, direct):
+                if not ok:
+                    d.copy_(s, non_blocking=True)
+            pairs = [p for p, ok in zip(pairs, direct) if ok]
+            tab = (_lib.CopyItem * max(1, len(pairs)))()
+            for it, (d, _) in zip(tab, pairs):
+                it.dst, it.bytes = d.data_ptr(), d.numel() * d.element_size()
+        for it, (_, s) in zip(tab, pairs):
+            it.src = s.data_ptr()
+        lib, stream = _lib.load(), _lib.stream(self.dev)
+        for i in range(0, len(pairs), _lib.COPY_MANY_MAX):
+            m = min(_lib.COPY_MANY_MAX, len(pairs) - i)
+            _lib.check(lib.coocc_copy_many(ctypes.byref(tab, i * ctypes.sizeof(_lib.CopyItem)), m, stream))
 
     # ------------------------------------------------------------------ search stage (helper threads)
     def _mark(self, t, tag):
@@ -174,10 +214,12 @@ class ServingPipeline:
         k, fr = t.slot, t.frame
         torch.cuda.set_device(self.dev)
         self._mark(t, "search_begin")
-        st = self.search_streams[k]
-        with torch.cuda.stream(st), torch.no_grad():
+        st = self.dense_streams[k % self.ndense] if self.lanes else self.search_streams[k]
+        # lanes: another slot's replay (or eager dense stage) may be issued on this stream by the issuing thread between two
+        # launches of this search, and another helper thread's search too -- the stage's per-stream scratch is the slot's own
+        with torch.cuda.stream(st), torch.no_grad(), core.scratch_space("search%d:" % k if self.lanes else ""):
             t.ready.wait(st)
-            if self.slot_done[k] is not None:
+            if self.slot_done[k] is not None and not self.lanes:
                 # the replay that read this slot last.  Waited for by THIS HOST THREAD (a sleeping wait), not by the stream: a
                 # second queue waiting for an event of a dense stream that has not fired yet cost the loop 15-20 % with three
                 # dense stages in flight -- 274 against 339 samples/s without the search stage, whichever queue waits and
@@ -224,7 +266,7 @@ class ServingPipeline:
                 sr = self.model.occ_fuser.search_native(pts, slot) if cg.NATIVE_SEARCH else \
                     self.model.occ_fuser.search(slot.img_rows().as_ncdhw(), pts, slot=slot)
             if self.time_dense:
-                if sr.done_side is not None:
+                if sr.done_side is not None and sr.done_side is not sr.done_main:
                     sr.done_side.wait(st)
                 e1 = cstreams_.new_event(timing=True)
                 e1.record()
@@ -232,15 +274,22 @@ class ServingPipeline:
         self._mark(t, "search_end")
         return sr
 
+    def _after_search(self, sr, ds):
+        """Dense stream ``ds`` waits for the search ``sr`` -- nothing to do for events that were recorded on ``ds`` itself (lanes: the
+        native search records one event, on the lane)."""
+        if self.lanes and sr.done_side is sr.done_main:
+            return
+        sr.done_main.wait(ds)
+        if sr.done_side is not None and sr.done_side is not sr.done_main:
+            sr.done_side.wait(ds)
+
     # ------------------------------------------------------------------ capture
     def _capture(self, example):
         for k in range(self.n):
             t = Ticket(self, -1, k, example, False)
             sr = self._search(t)
             ds = self.dense_streams[k % self.ndense]
-            sr.done_main.wait(ds)
-            if sr.done_side is not None:
-                sr.done_side.wait(ds)
+            self._after_search(sr, ds)
             self.graphs[k] = cg.DenseGraph(self.model, self.slots[k], self.static[k], ds, render=self.render).capture()
         torch.cuda.synchronize(self.dev)
         core.check_h2_overflow()
@@ -269,7 +318,8 @@ class ServingPipeline:
         while True:
             with self._lock:
                 # a ticket's search may start once its slot's previous occupant (n submits earlier) has had its replay ISSUED
-                # (the search then waits for that replay's event on the device), and at most `ahead` searches are in flight
+                # (lanes: on the stream the search goes to, so it runs behind it; else the helper thread waits for that replay's
+                # event first), and at most `ahead` searches are in flight
                 while self._pending and len(self._queue) < self.ahead:
                     t = self._pending[0]
                     if self._dispatched_of_slot[t.slot] > self._issued_of_slot[t.slot]:
@@ -302,9 +352,7 @@ class ServingPipeline:
     def _issue(self, t, sr):
         k = t.slot
         ds = self.dense_streams[k % self.ndense]
-        sr.done_main.wait(ds)
-        if sr.done_side is not None:
-            sr.done_side.wait(ds)
+        self._after_search(sr, ds)
         with torch.cuda.stream(ds), torch.no_grad():
             if self.time_dense:
                 e0 = cstreams_.new_event(timing=True)

@@ -91,6 +91,21 @@ int coocc_compact_flags_ex(const uint8_t* flags, int total, int32_t* lin, int32_
 int coocc_lin_to_coords(const int32_t* lin, int n, int X, int Y, int Z, float* xyz, int64_t* bxyz,
                         void* stream);
 
+/* Up to COOCC_COPY_MANY_MAX device -> device copies of contiguous buffers as ONE kernel launch on `stream` (the serving loop's
+ * per-frame inputs of the dense stage: megabytes of image features beside 36-byte camera matrices).  The table is read on the host
+ * and travels by value in the kernel arguments: no allocation, no host synchronisation, no memcpy node (capturable).  Items whose
+ * dst and src are both 16-byte aligned move as 16-byte vectors, the others as 4-byte words (bytes when an address is not 4-byte
+ * aligned), each with a word / byte tail; blocks are dealt over the items in proportion to their size.  Items must not overlap;
+ * bytes == 0 is allowed.  n outside 1 .. COOCC_COPY_MANY_MAX or a null pointer in a non-empty item: COOCC_EINVAL, nothing
+ * launched.  The reference has no counterpart: it hands each sample's tensors to the model by reference (COOCC_Ray.simple_test, coocc_ray.py:520). */
+#define COOCC_COPY_MANY_MAX 16
+typedef struct coocc_copy_item {
+  void* dst;
+  const void* src;
+  size_t bytes;
+} coocc_copy_item;
+int coocc_copy_many(const coocc_copy_item* items, int n, void* stream);
+
 /* ---------------------------------------------------------------- K2..K5 */
 
 /* [EXT] furthest_point_sampling_wrapper (M/ops/furthest_point_sample/src/

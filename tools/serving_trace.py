@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from co_occ_amd import streams  # noqa: E402
+from co_occ_amd import serving, streams  # noqa: E402
 
 
 def main():
@@ -52,6 +52,37 @@ def main():
         print("%5d  | %s %s %s %s %s %s | %8.2f .. %8.2f   %8.2f .. %8.2f  (%.2f)" % (
             idx - first, g("dispatch"), g("search_begin"), g("search_native"), g("search_end"), g("issue_begin"), g("issue_end"),
             s0, s1, base.elapsed_time(e0), base.elapsed_time(e1), e0.elapsed_time(e1)))
+    summary(gp, base, wall)
+
+
+def summary(gp, base, wall):
+    """What the table above says about the schedule: spans of the two stages, how long a dense stream idles between two replays and
+    what share of the window its replays fill, and how many launches carry a frame's dense-stage inputs into its slot."""
+    med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")
+    line = lambda name, v: print("%-72s: median %.2f  min %.2f  max %.2f" % (name, med(v), min(v), max(v)))
+    lanes = getattr(gp, "lanes", False)
+    print("search stage on %s" % ("its slot's dense stream (lanes)" if lanes else "a stream of its own per slot"))
+    line("device span of the search stage (Ticket.events), ms", [sev[0].elapsed_time(sev[1]) for _, _, _, sev in gp.dense_ev if sev])
+    line("dense span (events around the replay), ms", [e0.elapsed_time(e1) for e0, e1, _, _ in gp.dense_ev])
+    per, gaps, busy = {}, [], 0.0
+    for e0, e1, idx, sev in gp.dense_ev:
+        per.setdefault(idx % gp.n % gp.ndense, []).append((base.elapsed_time(e0), base.elapsed_time(e1), sev))
+    for k, v in sorted(per.items()):
+        busy += sum(b - a for a, b, _ in v)
+        gaps += [v[i + 1][0] - v[i][1] for i in range(len(v) - 1)]
+    line("idle gap of a dense stream between two replays, ms", gaps)
+    if lanes:        # the search of the next ticket sits in that gap: what of it is neither search nor replay
+        rest = []
+        for v in per.values():
+            rest += [v[i + 1][0] - v[i][1] - v[i + 1][2][0].elapsed_time(v[i + 1][2][1]) for i in range(len(v) - 1) if v[i + 1][2]]
+        line("... of which not the lane's own search stage, ms", rest)
+    print("dense streams busy over the window: %.1f ms of replays / (%d x %.1f ms) = %.0f %%" % (
+        busy, gp.ndense, 1e3 * wall, 100 * busy / (gp.ndense * 1e3 * wall)))
+    tab = getattr(gp, "_copy_tables", [None])[0]
+    st = gp.static[0]
+    ntens = 1 + len(st["cams"] or ()) + sum(torch.is_tensor(t) for t in st["transform"][:-1]) + (st["gemo"] is not None)
+    nl = ntens if tab is None or not getattr(serving, "COPY_MANY", False) else -(-len(tab) // 16)
+    print("dense-stage inputs of a frame: %d tensors copied into the slot by %d launch%s" % (ntens, nl, "" if nl == 1 else "es"))
 
 
 if __name__ == "__main__":
