@@ -151,7 +151,10 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
     launch per sample) of the current ones; a sample's SC / SSC confusion matrices (``coocc_eval_semantic``), its lidarseg labels
     and 16x16 matrix (``coocc_lidarseg_points``, when it carries ``points_occ``) and its fine-point count are computed on ITS dense stream right behind the replay and copied to pinned host memory asynchronously; the sample
     is yielded ``dense_streams`` issues later, when that copy has normally long finished.  A sample whose ``gt_occ`` is not the
-    captured fine grid (cascade_ratio x the coarse grid) takes ``model.simple_test`` (eager decode) in its turn.  Result tensors
+    captured fine grid (cascade_ratio x the coarse grid) takes ``model.simple_test`` (eager decode) in its turn -- when the head
+    has a fine branch; without one nothing is scattered and the metrics kernel resamples ``pred_c`` to any ground-truth grid.
+    Models without a fuser (camera-only ``COOCC_Ray``, ``COOCC_Ray_L``) run the same loop: their prefetch stage is the copy-in
+    and the slot fill (pooling, or the volume's layout kernel), with no index search.  Result tensors
     of a sample stay valid until ``slots`` more samples have been submitted: consume (or clone) them inside the loop body, as
     the upstream loop does.  ``stats`` (optional dict) receives ``fallbacks`` / ``recaptures`` / ``eager_samples``."""
     import collections
@@ -272,8 +275,9 @@ def pipelined_test(model, data_iter, slots=6, dense_streams=3, ahead=0, stats=No
                 gt = data.get("gt_occ")
                 X, Y, Z = pipe.grid
                 cf = model.pts_bbox_head.cascade_ratio
-                if gt is not None and list(gt.shape[1:]) != [X * cf, Y * cf, Z * cf]:
-                    # the captured scatter writes the default fine grid: this sample goes through simple_test's eager decode
+                if gt is not None and model.pts_bbox_head.has_fine_branch and list(gt.shape[1:]) != [X * cf, Y * cf, Z * cf]:
+                    # the captured scatter writes the default fine grid: this sample goes through simple_test's eager decode (a head
+                    # without a fine branch scatters nothing: the metrics kernel resamples pred_c to any gt grid)
                     keep, model.graph_simple_test = model.graph_simple_test, False
                     try:
                         res = model.simple_test(**{("img" if k == "img_inputs" else k): v for k, v in data.items()})

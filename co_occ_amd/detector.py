@@ -464,13 +464,14 @@ class COOCC_Ray(nn.Module):
         fr = dict(depth=pc.get("depth"), ctx=pc.get("ctx"), img_voxel_feats=pc.get("img_voxel_feats"), pts=pc.get("pts_voxel_feats"),
                   img_feats=pc.get("img_feats"), gemo=pc.get("gemo"), cams=pc.get("cams"),
                   transform=(img[1:] if img is not None else pc.get("transform")))
-        if precomputed is None:
+        if precomputed is None and img is not None:
             enc = self.image_encoder(img[0])
             rots, trans, intrins, post_rots, post_trans, bda = img[1:7]
             vt = self.img_view_transformer
             mlp_input = vt.get_mlp_input(rots, trans, intrins, post_rots, post_trans, bda)
             fr["depth"], fr["ctx"] = vt.lift([enc['x'], rots, trans, intrins, post_rots, post_trans, bda, mlp_input])
             fr["img_feats"] = enc['img_feats']
+        if precomputed is None and points is not None:
             fr["pts"] = self.extract_pts_feat(points)[0]
         if fr["cams"] is None and fr["gemo"] is None and fr["transform"] is not None:
             fr["cams"] = tuple(fr["transform"][:6])
@@ -480,13 +481,20 @@ class COOCC_Ray(nn.Module):
         """The dense stage of one frame through a one-slot ``ServingPipeline`` (built on first use, rebuilt when the shapes
         change).  Returns the output dict, or None when this configuration / frame cannot take the captured form."""
         from . import _lib
-        if fr["pts"] is None or fr["img_feats"] is None or fr["transform"] is None or (fr["depth"] is None and fr["img_voxel_feats"] is None):
+        camera = fr["depth"] is not None or fr["img_voxel_feats"] is not None
+        if self.occ_fuser is not None:
+            if fr["pts"] is None or fr["img_feats"] is None or fr["transform"] is None or not camera:
+                return None
+        elif camera == (fr["pts"] is not None):               # single modality: the camera volume or the LiDAR volume, not both
             return None
-        if fr["depth"] is not None and fr["cams"] is None:
+        if fr["depth"] is not None and (fr["cams"] is None or self.img_view_transformer is None):
             return None
         do_render = bool(self.use_rendering and self.test_rendering)
+        if do_render and not camera:
+            return None                                       # the LiDAR-only captured stage has no render block
+        one = next(fr[k] for k in ("pts", "depth", "img_voxel_feats") if fr[k] is not None)
         key = tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(fr.items()) if torch.is_tensor(v)) + \
-            (tuple(fr["img_feats"][0].shape), do_render, str(fr["pts"].device))
+            (tuple(fr["img_feats"][0].shape) if fr["img_feats"] is not None else None, do_render, str(one.device))
         if self._pipe1 is None or self._pipe1[0] != key:
             if self.graph_unavailable is not None and self.graph_unavailable[0] == key:
                 return None
@@ -519,7 +527,7 @@ class COOCC_Ray(nn.Module):
         pipe = self._pipe1[1]
         X, Y, Z = pipe.grid
         cf = self.pts_bbox_head.cascade_ratio
-        if fine_size is not None and list(fine_size) != [X * cf, Y * cf, Z * cf]:
+        if fine_size is not None and self.pts_bbox_head.has_fine_branch and list(fine_size) != [X * cf, Y * cf, Z * cf]:
             return None                                       # the captured scatter writes the default fine grid
         t = pipe.submit(fr, copy=True)
         out = dict(t.result(wait=True))
@@ -538,18 +546,28 @@ class COOCC_Ray(nn.Module):
         post_rots, post_trans, bda, ...); ``points`` = [points [N,5]].  ``precomputed=dict(img_voxel_feats= | depth= + ctx=,
         pts_voxel_feats=, gemo=, img_feats=)`` (an extension) bypasses the upstream encoders.
         In eval mode the dense stage runs as one captured hipGraph launch (``graph_simple_test``; same bits as the eager
-        launches, which remain the fallback for configurations / frames the captured form does not cover).
+        launches, which remain the fallback for configurations / frames the captured form does not cover).  So do the models
+        without a fuser -- the camera-only ``COOCC_Ray`` and ``COOCC_Ray_L`` (one ``graph.VoxelSlot`` instead of the search
+        slot; ``COOCC_Ray_L`` with ``test_rendering`` keeps the eager launches: its captured stage has no render block).  One
+        configuration is NOT bit-equal between the two routes: a voxel-only fine head (``sample_from_voxel=True,
+        sample_from_img=False``, cascade 2).  Its captured form (csrc/fine_vox.hip) applies ``fine_mlp[0]`` before the trilinear
+        interpolation, the eager form after it as the reference does; ``pred_f`` and the fine logits agree to fp32 rounding
+        (tests/test_gpu_fine_vox.py judges both against float64), ``pred_c`` and the fine coordinates bit for bit.
         ``points_occ`` ([points [N,>=4]], label in column 3; ``gt_occ`` may be None, the test-submission case) adds the lidarseg
         keys of coocc_ray.py:556-560, 648-651: ``output_points`` (int64 labels 1..16 on the device), ``target_points`` and
         ``evaluation_semantic`` (16x16 int64; a device tensor under ``metrics_on_device``)."""
         fine_size = list(gt_occ.shape[1:]) if gt_occ is not None else None
         out = None
         lifted = precomputed is not None and precomputed.get("depth") is not None
-        if (self.graph_simple_test or lifted) and not self.training and self.occ_fuser is not None and self.img_view_transformer is not None:
+        # the frame route: fused models with a view transformer, and single-modality models (no fuser: the camera-only COOCC_Ray,
+        # COOCC_Ray_L) -- those only when the captured form or a lifted pair asks for it, so that with graph_simple_test off their
+        # eager calls stay the launches they always were
+        framed = self.img_view_transformer is not None if self.occ_fuser is not None else True
+        if (self.graph_simple_test or lifted) and not self.training and framed:
             fr = self.serving_frame(img, points, img_metas, precomputed)
             out = self._simple_test_graph(fr, fine_size) if self.graph_simple_test else None
             if out is None:                                   # eager path from the frame that was just built
-                if fr["img_voxel_feats"] is None:
+                if fr["img_voxel_feats"] is None and fr["depth"] is not None:
                     fr["img_voxel_feats"] = self.img_view_transformer.lift_splat(fr["depth"], fr["ctx"], cams=fr["cams"])
                 gemo = fr["gemo"]
                 if gemo is None and fr["cams"] is not None and self.use_rendering and self.test_rendering:

@@ -216,6 +216,10 @@ class SearchSlot:
         self.near = torch.zeros(2, knum * V, device=device, dtype=_I32)     # near_img, near_pts (dense [K, count] inside)
         self._native = None
 
+    @property
+    def device(self):
+        return self.cat4.device
+
     def img_rows(self):
         X, Y, Z = self.grid
         return Rows(self.cat4, 1, X, Y, Z, self.C, 0, persistent=True)     # rewritten per frame by lift_splat(out=) / the search

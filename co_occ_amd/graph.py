@@ -14,7 +14,9 @@ stage capturable:
   neighbour tables -- written by the eager search stage on its own stream) and the sample's own tensors.
 
 The index search (K1-K5: FPS chains, top-K, ball query) stays eager on prefetch streams, one sample ahead, exactly as
-before: it is latency-bound on two CUs and hidden under the previous sample's dense stage.  Outputs of a replay are the
+before: it is latency-bound on two CUs and hidden under the previous sample's dense stage.  A single-modality model
+(camera-only ``COOCC_Ray`` with ``occ_fuser=None``, ``COOCC_Ray_L``) has no search: its slot is a ``VoxelSlot`` -- the
+frame's voxel volume as rows, filled eagerly (``fill_slot``) -- and the stage starts at the encoder.  Outputs of a replay are the
 graph's static tensors (``DenseGraph.out``): valid until the same graph is replayed again.
 
 ``tests/test_gpu_graph.py`` checks a replay bit for bit against the eager path on the same sample.
@@ -40,7 +42,8 @@ class DenseGraph:
 
     def _run(self):
         m, s = self.model, self.inputs
-        vf = m.occ_fuser.forward_static(self.slot)
+        # single-modality models (coocc_ray.py:255-256: no fuser): the slot's rows ARE the voxel features
+        vf = m.occ_fuser.forward_static(self.slot) if m.occ_fuser is not None else self.slot.rows()
         gemo, cam_geo = s.get("gemo"), None
         if self.render and s.get("cams") is not None:
             # P1 per sample (ViewTransformerLSSBEVDepth.py:117-150 via coocc_ray.py:186): the frustum geometry the render
@@ -49,7 +52,7 @@ class DenseGraph:
             cam_geo = m.img_view_transformer._camera_mats(*s["cams"])
             mats = cam_geo[0].reshape(-1, cam_geo[0].shape[-1])
             cam_geo = (mats,) + tuple(cam_geo[1:])
-        return m.decode(vf, gemo, s["img_feats"], s["transform"], self.render, static=True, cam_geo=cam_geo)
+        return m.decode(vf, gemo, s.get("img_feats"), s.get("transform"), self.render, static=True, cam_geo=cam_geo)
 
     def capture(self, warmup=2):
         """Eager warm-up on the capture stream (weight packs, per-stream scratch), then the capture itself."""
@@ -65,7 +68,7 @@ class DenseGraph:
         # counters): keep those tensors alive for as long as the graph exists.  A later eager call on the same stream that
         # needs a larger buffer REPLACES the registry's entry (core.stream_buffer) -- without this reference the old tensor
         # would be freed, handed to someone else by the caching allocator, and every replay would scribble over it.
-        dev = self.slot.cat4.device
+        dev = self.slot.device
         self._pinned = core.stream_scratch(dev, self.stream)
         for side in core.branch_streams_of(dev, self.stream):          # the stage's forked branches (core.Fork) have their own scratch
             self._pinned += core.stream_scratch(dev, side)
@@ -73,6 +76,8 @@ class DenseGraph:
 
     def fits(self, counts):
         """Host-side check of a sample's voxel counts against the capacities the graph was captured with."""
+        if self.model.occ_fuser is None:          # no voxel lists, no capacity: the stage runs on all V rows
+            return True
         Ni, Np = counts
         from . import fuser
         split = fuser.SPLIT_C0 or self.slot.V > fuser.DENSE_C0_MAX_VOXELS
@@ -93,6 +98,70 @@ def search_into_slot(model, slot, depth, ctx, cams, pts):
     return model.occ_fuser.search(img, pts, slot=slot)
 
 
-def make_slot(model, grid, device):
+class VoxelSlot:
+    """The sample slot of a single-modality model (``occ_fuser is None``): one static [V, C] fp32 rows buffer -- the pooled camera
+    volume or the LiDAR volume of the frame bound to the slot -- that the captured dense stage reads as its voxel features.  What
+    ``SearchSlot`` is to the fused model, without counts, voxel lists or neighbour tables."""
+
+    def __init__(self, C, grid, device):
+        X, Y, Z = (int(v) for v in grid)
+        C = int(C)
+        if min(X, Y, Z, C) <= 0:
+            raise ValueError("VoxelSlot: grid %r x %r channels" % (tuple(grid), C))
+        self.grid, self.C, self.V = (X, Y, Z), C, X * Y * Z
+        self.t = torch.zeros(self.V, C, device=device, dtype=torch.float32)
+
+    @property
+    def device(self):
+        return self.t.device
+
+    def rows(self):
+        X, Y, Z = self.grid
+        return core.Rows(self.t, 1, X, Y, Z, self.C, 0, persistent=True)      # rewritten per frame by lift_splat(out=) / fill_volume
+
+    img_rows = rows
+
+
+def slot_channels(model, example=None):
+    """Channels of a single-modality model's voxel features: ``numC_Trans`` of the view transformer, else those of the frame's
+    LiDAR volume."""
+    vt = getattr(model, "img_view_transformer", None)
+    if vt is not None:
+        return int(vt.numC_Trans)
+    vol = (example or {}).get("pts")
+    if vol is None:
+        raise ValueError("make_slot: a model without fuser and view transformer takes its channel count from a LiDAR volume (pts)")
+    return int(vol.shape[1])
+
+
+def make_slot(model, grid, device, example=None):
     f = model.occ_fuser
+    if f is None:
+        return VoxelSlot(slot_channels(model, example), grid, device)
     return SearchSlot(f.in_channels, f.knum, grid, device)
+
+
+def fill_volume(slot, vol):
+    """A [1,C,X,Y,Z] volume (any strides) -> the slot's rows, on the current stream: the layout kernel writing into the static
+    buffer, or one flat copy when the volume already is channels-last."""
+    r = slot.rows()
+    if tuple(vol.shape) != (1, r.C, r.X, r.Y, r.Z):
+        raise ValueError("fill_volume: volume %r for a slot of %r" % (tuple(vol.shape), (1, r.C, r.X, r.Y, r.Z)))
+    vol = vol.float()
+    cl = vol.permute(0, 2, 3, 4, 1)
+    if cl.is_contiguous():
+        r.t.copy_(cl.reshape(r.V, r.C), non_blocking=True)
+    else:
+        _lib.call("coocc_ncdhw_to_ndhwc", _lib.ptr(vol.contiguous()), _lib.ptr(r.t), 1, r.C, r.V, r.C, 0)
+    return r
+
+
+def fill_slot(model, slot, fr):
+    """The voxel features of one single-modality frame -> the slot's rows on the CURRENT stream (outside the graph: the pooling
+    workspace's "left clean" mark lives on a host object, ``ops.pool_ws_clean``, and a capture would freeze it)."""
+    if fr.get("depth") is not None:
+        model.img_view_transformer.lift_splat(fr["depth"], fr["ctx"], cams=fr["cams"], out=slot.rows())
+    elif fr.get("img_voxel_feats") is not None:
+        fill_volume(slot, fr["img_voxel_feats"])
+    else:
+        fill_volume(slot, fr["pts"])

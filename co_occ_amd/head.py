@@ -127,6 +127,10 @@ class OccHead(nn.Module):
             if hasattr(self, "fine_mlp"):
                 d["fine0"] = PackedConv(self.fine_mlp[0].weight, bias=self.fine_mlp[0].bias)
                 d["fine3"] = PackedConv(self.fine_mlp[3].weight, bias=self.fine_mlp[3].bias)
+                if not hasattr(self, "img_mlp") and self.fine_mlp[0].weight.shape[1] == 128:
+                    # voxel-only head: fine_mlp[0] without its bias, applied to the coarse rows BEFORE the resampling
+                    # (csrc/fine_vox.hip adds the bias behind it)
+                    d["f0_nb"] = PackedConv(self.fine_mlp[0].weight)
             if hasattr(self, "img_mlp"):
                 d["img0"] = PackedConv(self.img_mlp_0[0].weight.flatten(1), bias=self.img_mlp_0[0].bias)
                 d["img"] = PackedConv(self.img_mlp[0].weight, bias=self.img_mlp[0].bias)
@@ -388,12 +392,23 @@ class OccHead(nn.Module):
         """The fused (Linear-first) fine branch with the foreground count on the device; see ``_fine(static=True)``."""
         dev = ovf.t.device
         V, r = ovf.V, self.cascade_ratio
+        if g is None and self._fine_vox_ok(p, ovf):
+            # voxel-only head, ratio 2: Q = fine_mlp[0].weight . rows on the coarse grid, then everything else in one launch with the
+            # count on the device (csrc/fine_vox.hip).  The eager ``_fine`` samples the 128-channel rows first and applies the Linear
+            # afterwards, as the reference does: the two forms agree to rounding, not bit for bit
+            fine_xyz = torch.empty(3 * V * 8, device=dev, dtype=_I64)
+            self._note_fine(dict(xyz=fine_xyz, lin=lin, n=V, cnt=cnt, coarse=(ovf.X, ovf.Y, ovf.Z), map=fgmap))
+            Q = linear_rows(ovf.t, p["f0_nb"], in_coff=ovf.coff, in_C=128)
+            logits = torch.empty(V * 8, self.out_channel, device=dev, dtype=_F32)
+            self._fine_vox(ovf, Q, lin, V, cnt, fine_xyz, logits)
+            return logits, fine_xyz, cnt
         ok = (FUSED_FINE_MLP and FINE_LINEAR_FIRST and g is not None and self.sample_from_voxel and ovf.C == 128 and g.shape[1] == 128
               and self.out_channel <= 32 and self.img_mlp[1].num_groups == 16 and self.fine_mlp[1].num_groups == 16
               and p.get("mlp_aligned", False) and "img_nb" in p and r in (2, 4))
         if not ok:
             raise _lib.CooccArgError("OccHead static fine branch: only the fused Linear-first configuration (cascade 2 / 4, image + "
-                                  "voxel samples, 128-channel features) has device-count kernels")
+                                  "voxel samples, 128-channel features) and the voxel-only head at cascade 2 (128-channel features, "
+                                  "final_occ_size = 2 x the coarse grid) have device-count kernels")
         N_i, Hf, Wf = img_dims
         nf = V * r ** 3
         fine_xyz = torch.empty(3 * nf, device=dev, dtype=_I64)
@@ -419,6 +434,25 @@ class OccHead(nn.Module):
              float(gi.eps), d(l0.weight), d(l0.bias), d(g0.weight), d(g0.bias), float(g0.eps), d(l3.weight), d(l3.bias),
              self.out_channel, ptr(logits))
         return logits, fine_xyz, cnt
+
+    def _fine_vox_ok(self, p, ovf):
+        """The one-launch voxel-only fine branch (csrc/fine_vox.hip): ratio 2, 128-channel rows, 64 hidden channels in 16 GroupNorm
+        groups, <= 32 classes, final grid = 2 x coarse grid, 16-byte aligned parameters."""
+        if not (self.sample_from_voxel and "f0_nb" in p and self.cascade_ratio == 2 and ovf.C == 128 and self.out_channel <= 32):
+            return False
+        l0, g0, l3 = self.fine_mlp[0], self.fine_mlp[1], self.fine_mlp[3]
+        return (l0.weight.shape[0] == 64 and g0.num_groups == 16 and l0.bias is not None and l3.bias is not None
+                and tuple(int(v) for v in self.final_occ_size) == (2 * ovf.X, 2 * ovf.Y, 2 * ovf.Z)
+                and all(t.data_ptr() % 16 == 0 and t.is_contiguous() and t.dtype == _F32 for t in (l0.bias, g0.weight, g0.bias, l3.weight)))
+
+    def _fine_vox(self, ovf, Q, lin, n_cap, cnt, fine_xyz, logits):
+        l0, g0, l3 = self.fine_mlp[0], self.fine_mlp[1], self.fine_mlp[3]
+        d = lambda t: ptr(t.detach())
+        # bytes: the Q rows read once, logits + coordinates written
+        with TIMER.region("k_fine_vox", 256.0 * ovf.V + 8.0 * n_cap * (4 * self.out_channel + 24)):
+            call("coocc_fine_vox", ptr(Q), ovf.X, ovf.Y, ovf.Z, ptr(lin), int(n_cap), ptr(cnt, _I32) if cnt is not None else None,
+                 host_i32(self.final_occ_size), d(l0.bias), d(g0.weight), d(g0.bias), float(g0.eps), d(l3.weight), d(l3.bias),
+                 self.out_channel, ptr(fine_xyz), ptr(logits))
 
     def _fine2_h2_ok(self):
         """Ratio 2 on the split-f16 engine: the points-as-lanes one-launch kernel (csrc/fine2_h2.hip)."""
@@ -472,6 +506,11 @@ class OccHead(nn.Module):
         return params
 
     # ---------------------------------------------------------------- forward
+    @property
+    def has_fine_branch(self):
+        """occ_head.py:173: the cascade runs (and the head returns fine outputs) only with a ratio and something to sample from."""
+        return bool(self.cascade_ratio != 1 and (self.sample_from_img or self.sample_from_voxel))
+
     def draw_fine_voxels(self, logit_rows, generator=None):
         """Coarse voxels whose ``ratio^3`` children the fine branch evaluates: foreground = argmax != empty; in training
         at most ``fine_topk`` of them, drawn at random (coordinate_transform.py:17-21 permutes the COARSE columns and keeps

@@ -18,6 +18,11 @@ reference's call):
   ``DenseGraph``: one launch on one of ``dense_streams`` streams.  A frame whose LiDAR sweep is denser than the captured
   capacity takes the eager dense stage (``eager_fallbacks``).
 
+A model WITHOUT a fuser (the camera-only ``COOCC_Ray`` with ``occ_fuser=None``; ``COOCC_Ray_L``) goes through the same loop: its slot
+is a ``graph.VoxelSlot`` (the frame's voxel volume as rows), its prefetch stage is the copy-in, the slot fill (pooling from ``depth`` /
+``ctx`` / ``cams``, or the layout kernel from an ``img_voxel_feats`` / ``pts`` volume; raw ``points`` run ``extract_pts_feat`` first)
+and one event on the lane -- no index search, no counts, so the dense stage always replays.  The LiDAR-only stage has no render block.
+
 ``Ticket.result()`` hands back the graph's output tensors (valid until the slot is reused ``slots`` submits later; ask for
 ``copy=True`` to own them) after checking the split-f16 engine's range guard.  Everything here is stream-ordered: results are
 bit-identical to sequential eager calls (tests/test_gpu_serving.py).
@@ -90,6 +95,37 @@ def _clone_frame_item(v):
     return v
 
 
+def check_frame(model, fr):
+    """The form of frame ``fr`` for ``model``: "fused" (camera + LiDAR, a model with a fuser), "camera" (``depth`` + ``ctx`` + ``cams``,
+    or ``img_voxel_feats``; ``occ_fuser is None``) or "lidar" (``pts`` or raw ``points``; ``occ_fuser is None``).  Raises
+    ``ValueError`` for a frame the model cannot serve."""
+    has = lambda k: fr.get(k) is not None
+    camera, lidar = has("depth") or has("img_voxel_feats"), has("pts") or has("points")
+    if has("depth") and not (has("ctx") and has("cams")):
+        raise ValueError("serving frame: depth comes with ctx and cams (the lifted pair and the camera matrices)")
+    if has("depth") and getattr(model, "img_view_transformer", None) is None:
+        raise ValueError("serving frame: depth / ctx need the model's view transformer; pass img_voxel_feats")
+    if model.occ_fuser is not None:
+        if not (camera and lidar):
+            raise ValueError("serving frame: a fused model takes a camera part (depth + ctx + cams | img_voxel_feats) and a LiDAR "
+                             "part (pts | points)")
+        return "fused"
+    if camera == lidar:
+        raise ValueError("serving frame: a model without fuser takes a camera part (depth + ctx + cams | img_voxel_feats) or a "
+                         "LiDAR part (pts | points), not %s" % ("both" if camera else "neither"))
+    return "camera" if camera else "lidar"
+
+
+class _SlotFilled:
+    """What the prefetch stage of a single-modality frame hands to the dense stage: one event on the stream that filled the slot
+    (the members of a ``fuser.SearchResult`` the loop reads; no voxel counts)."""
+
+    def __init__(self):
+        self.done_main = self.done_side = cstreams_.new_event()
+        self.done_main.record()
+        self.counts = None
+
+
 class ServingPipeline:
     """``model``: a ``COOCC_Ray`` in eval mode.  ``example``: one frame (dict, see ``submit``) that fixes the shapes; it is
     used for the warm-up and the capture of every slot.  ``after_done(out, event)`` (optional) is called on the issuing thread with the completion event of the frame's replay
@@ -100,14 +136,26 @@ class ServingPipeline:
                  time_dense=False, after_done=None, search_lanes=None):
         assert not model.training, "ServingPipeline serves the eval-mode (folded-BN) path"
         self.model = model
+        check_frame(model, example)
         pts = example.get("pts")
-        if pts is None:            # raw LiDAR points: the producer (voxelisation + VFE + sparse encoder) runs in the search stage
+        if pts is None and example.get("points") is not None:
+            # raw LiDAR points: the producer (voxelisation + VFE + sparse encoder) runs in the search stage
             with torch.no_grad():
                 pts = model.extract_pts_feat(example["points"])[0]
-        self.dev = dev = pts.device
-        _, _, X, Y, Z = pts.shape
+        vt = getattr(model, "img_view_transformer", None)
+        if pts is not None:
+            vol = pts
+        elif vt is not None and example.get("depth") is not None:      # camera-only: the pooling grid of the view transformer
+            vol = None
+        else:
+            vol = example["img_voxel_feats"]
+        self.dev = dev = vol.device if vol is not None else example["depth"].device
+        X, Y, Z = vt._grid_host()[0] if vol is None else vol.shape[2:]
         self.grid = (X, Y, Z)
-        self.render = (X >= 100 and Y >= 100 and Z >= 8 and model.use_rendering) if render is None else render
+        lidar_only = model.occ_fuser is None and pts is not None
+        if lidar_only and render:
+            raise NotImplementedError("ServingPipeline: the LiDAR-only captured stage has no render block")
+        self.render = (X >= 100 and Y >= 100 and Z >= 8 and model.use_rendering and not lidar_only) if render is None else render
         self.n = n = max(1, int(slots))
         self.ndense = max(1, min(int(dense_streams), max(1, n - 1)))
         # searches in flight ahead of the dense stage: at most slots - dense streams (a slot is rewritten only after the replay
@@ -129,7 +177,7 @@ class ServingPipeline:
         # queues a process gets by default nothing shares a queue (profiles/search_lanes_*.txt).  search_lanes=False:
         # one search stream per slot next to the dense streams, ordered by events (more queues than streams: 16 and up).
         self.search_streams = None if self.lanes else [torch.cuda.Stream(device=dev, priority=search_priority) for _ in range(n)]
-        self.slots = [cg.make_slot(model, self.grid, dev) for _ in range(n)]
+        self.slots = [cg.make_slot(model, self.grid, dev, example=dict(pts=pts)) for _ in range(n)]
         self.static = [self._make_static(example) for _ in range(n)]
         self._copy_tables = [None] * n
         self.slot_done = [None] * n            # event: the last replay that read slot k
@@ -160,13 +208,13 @@ class ServingPipeline:
     def _make_static(self, fr):
         dev = self.dev
         cams = fr.get("cams")
-        tr = fr["transform"]
-        size = tr[-1]
-        size = tuple(int(v[0]) if torch.is_tensor(v) else int(v) for v in size)       # image size: fixed per pipeline
-        st = dict(img_feats=[torch.empty_like(fr["img_feats"][0], device=dev)],
+        tr, feats = fr.get("transform"), fr.get("img_feats")         # both absent: LiDAR-only
+        if tr is not None:
+            size = tuple(int(v[0]) if torch.is_tensor(v) else int(v) for v in tr[-1])       # image size: fixed per pipeline
+            tr = tuple(torch.empty_like(t, device=dev) if torch.is_tensor(t) else t for t in tr[:-1]) + (size,)
+        st = dict(img_feats=[torch.empty_like(feats[0], device=dev)] if feats is not None else None,
                   cams=tuple(torch.empty_like(t, device=dev) for t in cams) if cams is not None else None,
-                  transform=tuple(torch.empty_like(t, device=dev) if torch.is_tensor(t) else t for t in tr[:-1]) + (size,),
-                  gemo=None)
+                  transform=tr, gemo=None)
         if cams is None:                       # geometry tensor instead of camera matrices (render reads it)
             st["gemo"] = torch.empty_like(fr["gemo"], device=dev) if fr.get("gemo") is not None else None
         return st
@@ -174,12 +222,15 @@ class ServingPipeline:
     def _copy_in(self, k, fr):
         """The new frame's dense-stage inputs -> slot k's static tensors (on the current stream: the slot's lane / search stream)."""
         st = self.static[k]
-        pairs = [(st["img_feats"][0], fr["img_feats"][0])]
+        pairs = [(st["img_feats"][0], fr["img_feats"][0])] if st["img_feats"] is not None else []
         if st["cams"] is not None:
             pairs += zip(st["cams"], fr["cams"])
-        pairs += [(d, s) for d, s in zip(st["transform"][:-1], fr["transform"][:-1]) if torch.is_tensor(d)]
+        if st["transform"] is not None:
+            pairs += [(d, s) for d, s in zip(st["transform"][:-1], fr["transform"][:-1]) if torch.is_tensor(d)]
         if st["gemo"] is not None:
             pairs.append((st["gemo"], fr["gemo"]))
+        if not pairs:                          # LiDAR-only: the dense stage reads the slot's rows and nothing else
+            return
         # one launch for all of them (coocc_copy_many, csrc/layout.hip): the table of the slot is built once -- the destinations
         # are static -- and only the sources change per frame.  A source that is not a contiguous device tensor of the
         # destination's type and shape goes through copy_ (which converts / gathers / uploads).
@@ -239,12 +290,19 @@ class ServingPipeline:
             if not diag & 1:
                 self._copy_in(k, fr)
             pts = fr.get("pts")
-            if pts is None:        # coocc_ray.py:215-234: points -> Voxelization -> HardSimpleVFE -> SparseLiDAREnc8x -> [1,C,X,Y,Z]
+            if pts is None and fr.get("points") is not None:
+                # coocc_ray.py:215-234: points -> Voxelization -> HardSimpleVFE -> SparseLiDAREnc8x -> [1,C,X,Y,Z] (COOCC_Ray_L: + the trunk)
                 pts = self.model.extract_pts_feat(fr["points"])[0]
             t.pts_vol = pts
             self._mark(t, "search_native")
             slot = self.slots[k]
-            if diag & 6 and fr.get("depth") is not None and self._last_sr[k] is not None:
+            if self.model.occ_fuser is None:
+                # single modality: no index search -- the frame's volume into the slot's rows (pooling, or the layout kernel), then
+                # an event on the lane
+                if not diag & 2:
+                    cg.fill_slot(self.model, slot, fr if pts is fr.get("pts") else dict(fr, pts=pts))
+                sr = _SlotFilled()
+            elif diag & 6 and fr.get("depth") is not None and self._last_sr[k] is not None:
                 # DIAGNOSTIC ONLY (COOCC_SERVING_DIAG_SKIP, tools/pipeline_gap.py): leave out the pooling (2) and / or the index search
                 # (4) of this frame and replay the slot's previous contents -- results are those of the slot's LAST searched frame
                 if not diag & 2:
@@ -298,7 +356,10 @@ class ServingPipeline:
     def submit(self, frame, copy=False):
         """``frame``: dict(depth [N,D,fH,fW], ctx [N,C,fH,fW], cams=(rots, trans, intrins, post_rots, post_trans, bda),
         pts [1,C,X,Y,Z], img_feats=[[1,N,512,fH,fW]], transform=img_inputs[1:]) -- or ``img_voxel_feats`` [1,C,X,Y,Z] instead
-        of depth / ctx, and / or raw LiDAR ``points`` [n,F] instead of ``pts`` (the LiDAR producer then runs in the search stage).  Shapes as the example's.  Returns a ``Ticket``.  The frame's tensors are read by the prefetched
+        of depth / ctx, and / or raw LiDAR ``points`` [n,F] instead of ``pts`` (the LiDAR producer then runs in the search stage).
+        A model without a fuser takes the camera part alone -- dict(depth, ctx, cams, img_feats, transform) or
+        dict(img_voxel_feats, img_feats, transform[, gemo]) -- or the LiDAR part alone -- dict(pts) or dict(points)
+        (``check_frame``).  Shapes as the example's.  Returns a ``Ticket``.  The frame's tensors are read by the prefetched
         search: do not overwrite them before ``Ticket.result()``.  If the model's weights changed since the capture (optimizer
         step, ``load_state_dict``, ``.to()``, ``invalidate_packs``) everything in flight is drained and the slots are captured
         again first -- result tensors of earlier tickets must have been consumed by then."""

@@ -784,6 +784,18 @@ int coocc_fine_sample_img_lin(const float* img_nhwc, int ncam, int Ci, int Hf, i
                               const int32_t* coarse_lin, int Yc, int Zc, int n_cap, const int32_t* n_dev, float* feat,
                               int out_stride, int ratio, void* stream);
 
+/* The fine branch of a VOXEL-ONLY head (occ_head.py:205-214, 237 with sample_from_voxel and no image samples), cascade ratio 2, in
+ * ONE launch (csrc/fine_vox.hip).  Q: [X*Y*Z, 64] = fine_mlp[0].weight . out_voxel_feats WITHOUT bias (the Linear applied before
+ * the interpolation it commutes with); coarse_lin: the foreground coarse voxels, at most n_cap of them -- n_dev != NULL: the count
+ * is read on the device (min(n_cap, *n_dev)), NULL: n_cap is the count; final_size_host = 2 * (X, Y, Z).  Per child of each
+ * listed voxel: trilinear sample of Q (align_corners=False, zero padding) + b_f0 -> GroupNorm(16 groups of 4) -> ReLU ->
+ * Linear 64 -> ncls (ncls <= 32).  Outputs as coocc_fine_sample_voxel: fine_xyz [3][8 n] packed at the start of the buffer,
+ * out [8 n, ncls], row o * n + i (child-offset major); rows past 8 n are not written.  Q, w_f3 and the 64-float vectors must be
+ * 16-byte aligned.  No atomics: the same bits from run to run. */
+int coocc_fine_vox(const float* Q, int X, int Y, int Z, const int32_t* coarse_lin, int n_cap, const int32_t* n_dev,
+                   const int* final_size_host, const float* b_f0, const float* gn_f0_w, const float* gn_f0_b, float eps_f0,
+                   const float* w_f3, const float* b_f3, int ncls, int64_t* fine_xyz, float* out, void* stream);
+
 /* ---------------------------------------------------------------- R1..R3, L1 */
 /* inline render block, one launch for all cameras (P/coocc/detectors/coocc_ray.py:575-616).
  * table:[X*Y*Z,4] = raw (sigma, r, g, b) head outputs per voxel -- the heads are pointwise,
